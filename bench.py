@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: multimodal training-step throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config teacher|student|probe] [--strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config teacher|student|probe] [--strong] [--full] [--dump-outputs DIR]
 
 --config teacher (default; BASELINE.json configs[2], the configuration the metric is quoted on): full `dual_patch` teacher —
     CXR 224x224 through a frozen ViT-B/14 + frozen DuETT over T=96 / V=48 vitals + trainable pathology-query fusion head, batch
@@ -13,18 +13,31 @@
 
 One step = the whole step function: `feats_to_input` (device kernel), forward of every encoder, loss, backward of every trainable
 parameter, gradient all-reduce when N > 1, optimiser step, scheduler step.
-`value` is the rate with the batches RESIDENT IN HBM when the timed region starts (the driver's contract).  The PCIe-INCLUSIVE rate
-(batches in pinned host memory, as a DataLoader(pin_memory=True) hands them over, staged one call ahead on a copy
-stream) is measured right after the timed region and reported as `config.pcie_inclusive_samples_per_s`; `--host-batches` swaps the two.
-`ms_per_step_median`: per-step HIP events over max(steps, 50) further steps.
+`value` is the rate with the batches RESIDENT IN HBM when the timed region starts (the driver's contract); `ms_per_step` is the wall
+time of the K timed steps divided by K.
+
+A plain run sets up, warms up (W steps), times the K steps, writes `--dump-outputs` and prints the line: nothing else.  `--full` adds
+the side measurements, all taken after the timed region:
+  - the PCIe-INCLUSIVE rate (batches in pinned host memory, as a DataLoader(pin_memory=True) hands them over, staged
+    one call ahead on a copy stream), reported as `config.pcie_inclusive_samples_per_s`; `--host-batches` swaps the two;
+  - `ms_per_step_median`: per-step HIP events over max(steps, 50) further steps;
+  - `config.hw_queue_phase`: graph_step's hardware-queue phase check (MEDP_PHASE_CHECK);
+  - `roofline.isolated` and `roofline.hbm_kernels` (isolated launches), `cpu_baseline` (the CPU oracle).
+Without `--full` those fields are null.  `roofline` itself (in-kernel launch clocks of the GEMMs inside the timed region) costs no run
+of its own and is reported by both.
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the last timed step computed as float32 / float64 `DIR/<name>.npy`:
+`out.<key>` for every entry of the step's output dict, `param.<name>` for every trainable parameter after its update (a fixed, seeded
+sample, `param.<name>.sample`, when all of them exceed the 60-MB budget).  Inputs and weights are seeded: the same arguments give the
+same inputs on every run, so two builds can be compared output for output (`--dump-outputs bench_outputs/A`: that folder is git-ignored).
 
 N > 1: `python bench.py --gpus N` starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process
 before any GPU call and relays rank 0's JSON line; under torch.distributed.run (RANK set) it is one rank per GPU over RCCL.
 Weak scaling (default, accelerate's semantics: 64 samples per GPU) or --strong (global batch 64 sharded: 64/N per GPU).
 
 Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` (the dominant kernel = the CXR-encoder block GEMMs,
-timed IN the timed region by in-kernel launch clocks, and isolated with HIP events; the HBM-bound DuETT / norm kernels against
-8 TB/s) and `cpu_baseline` (the CPU oracle timed on the host cores, N=1 only).
+timed IN the timed region by in-kernel launch clocks, and, with --full, isolated with HIP events; the HBM-bound DuETT / norm kernels
+against 8 TB/s) and, with --full, `cpu_baseline` (the CPU oracle timed on the host cores, N=1 only).
 """
 from __future__ import annotations
 
@@ -56,7 +69,12 @@ def parse_args():
     ap.add_argument("--config", choices=("teacher", "student", "probe"), default="teacher")
     ap.add_argument("--batch", type=int, default=64, help="batch: per GPU (weak scaling, accelerate semantics) or global (--strong)")
     ap.add_argument("--strong", action="store_true", help="strong scaling: the global batch (--batch, 64) is sharded, 64/N per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the side measurements after the timed region (PCIe-inclusive rate, per-step median, hardware-queue "
+                         "phase check, isolated GEMM / HBM kernel timings, CPU baseline); off: only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="graph mode: run the frozen part inside its own batch's step instead of one batch ahead")
     ap.add_argument("--resident", action="store_true", help="(default since round 3; kept for old command lines) time the step on HBM-resident batches")
@@ -67,7 +85,7 @@ def parse_args():
                     help="train the CXR encoder too (run.py --unfreeze_cxr; SURVEY 8f1): a side measurement, never the contract line")
     ap.add_argument("--stress", action="store_true",
                     help="BASELINE.json configs[4] shapes per GPU (CXR 512x512, T=256, F=96, batch 32 = 256 / 8 GPUs); a side measurement")
-    ap.add_argument("--no-hbm-table", action="store_true", help="skip the per-kernel HBM table of the roofline object")
+    ap.add_argument("--no-hbm-table", action="store_true", help="(--full) skip the per-kernel HBM table of the roofline object")
     ap.add_argument("--launch-check", action="store_true",
                     help="no GPU work: every rank joins a gloo group, takes part in the barrier / MAX-over-ranks timing exchange and rank 0 "
                          "prints a JSON line - checks the self-launch, rendezvous and relay path on a CPU box (tests/test_bench_launch.py)")
@@ -279,6 +297,38 @@ def hbm_kernel_table(B, T, V, device, duett=None):
              "GBps": round(by / c * 1e-3, 1), "frac_of_hbm_peak": round(by / c * 1e-3 / PEAK_HBM_GBS, 4)} for nm, by, c, w_, n in rows]
 
 
+def dump_outputs(path, out, trainable, budget_bytes=60 << 20):
+    """--dump-outputs: the step's output dict (`out.<key>`: tensors as float32, float64 kept; Python numbers as float64 scalars) and
+    every trainable parameter after the step's update (`param.<name>`).  When outputs and parameters together exceed `budget_bytes`,
+    each parameter is replaced by the same fraction of its elements, drawn by a generator of fixed seed (`param.<name>.sample`,
+    flattened, in index order): the same arguments pick the same elements on every run."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            t = v.detach().cpu()
+            arrays[f"out.{k}"] = (t if t.dtype == torch.float64 else t.float()).numpy()
+        elif isinstance(v, (int, float)):
+            arrays[f"out.{k}"] = np.array(v, dtype=np.float64)
+    params = [(n, p) for n, p in trainable.named_parameters() if p.requires_grad]
+    left = budget_bytes - sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, left / max(4 * sum(p.numel() for _, p in params), 1))
+    gen = torch.Generator().manual_seed(0)
+    for n, p in params:
+        t = p.detach().float().cpu()
+        if frac < 1.0:
+            t = t.reshape(-1)
+            idx = torch.randperm(t.numel(), generator=gen)[:max(1, int(t.numel() * frac))].sort().values
+            t, n = t[idx], n + ".sample"
+        arrays[f"param.{n}"] = t.numpy()
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays, {sum(a.nbytes for a in arrays.values()) / 2**20:.1f} MiB -> {path}",
+          file=sys.stderr, flush=True)
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -394,7 +444,8 @@ def main():
     graph_error = None
     if want_graph:
         from multimodal_edema_prediction_amd.graph_step import GraphedStudentStep, GraphedTeacherStep
-        os.environ.setdefault("MEDP_PHASE_CHECK", "1")          # report which hardware-queue phase the captured step sits in (graph_step._setup)
+        if args.full:
+            os.environ.setdefault("MEDP_PHASE_CHECK", "1")      # report which hardware-queue phase the captured step sits in (graph_step._setup)
         arm = lambda: abi.check(L.medp_gemm_profile_enable(2), "gemm_profile_enable")     # launch clocks ride in the captured GEMMs
         disarm = lambda: L.medp_gemm_profile_enable(0)                                       # ... and only in those (not in later eager launches)
         try:
@@ -418,6 +469,7 @@ def main():
             if int(okt.item()) == 0:
                 gstep = None
                 graph_error = graph_error or "another rank failed to build the captured step"
+    last_out = [None]                                   # the output dict of the latest step, as the step function returned it
     if gstep is None:
         if world > 1:
             reducer = dp.GradAllReducer([p for p in trainable.parameters() if p.requires_grad]).attach(opt)
@@ -459,6 +511,7 @@ def main():
                     loss.backward()
                     opt.step()
                     out = {"loss": loss.detach()}
+            last_out[0] = out
             if sched is not None:
                 sched.step()
             return out
@@ -477,6 +530,7 @@ def main():
                                  pool[(i + 2) % n_pool] if (host and pipeline) else None)   # host batches: the one after, staged ahead)
             else:
                 out = gstep.step(pool[i % n_pool], pool[(i + 1) % n_pool], pool[(i + 2) % n_pool] if (host and pipeline) else None)
+            last_out[0] = out
             sched.step()
             k = _state["n"]
             _pin[k % 2].copy_(out["loss"], non_blocking=True)
@@ -516,8 +570,8 @@ def main():
             dt = float(tt.item())
         return dt
 
-    # `value`: batches RESIDENT in HBM when the timed region starts; the PCIe-inclusive rate (pinned host batches, staged one call
-    # ahead, `feats_to_input` inside the step) is measured right after it and reported in `config` (--host-batches swaps the two)
+    # `value`: batches RESIDENT in HBM when the timed region starts; with --full the PCIe-inclusive rate (pinned host batches, staged
+    # one call ahead, `feats_to_input` inside the step) is measured right after it and reported in `config` (--host-batches swaps the two)
     main_pool = host_pool if args.host_batches else dev_pool
     if gstep is None:                                   # eager steps: HIP events bracket the GEMM launches inside the timed region
         for i in range(args.warmup):
@@ -525,10 +579,11 @@ def main():
         if probe_graph is None:
             L.medp_gemm_profile_enable(1)
         dt = timed(main_pool, args.steps, 0, first=args.warmup)
-        last_loss = float(run_step(main_pool, 0)["loss"])
     else:
         dt = timed(main_pool, args.steps, args.warmup)
-        last_loss = float(gstep.out["loss"].item())
+    last_loss = float(last_out[0]["loss"])
+    if args.dump_outputs and rank == 0:                 # before any side measurement trains further
+        dump_outputs(args.dump_outputs, last_out[0], trainable)
     # ---- roofline leg 1: the dominant kernel IN the timed region -------------------------------------------------------------
     ms, n_l, fl = ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double()
     in_step = None
@@ -538,27 +593,27 @@ def main():
         if n_l.value > 0 and ms.value > 0:
             in_step = {"achieved": fl.value / (ms.value * 1e-3) / 1e12, "launches": int(n_l.value),
                        "avg_launch_us": ms.value * 1e3 / n_l.value, "flops_per_launch": fl.value / n_l.value}
-    # ---- side measurements: the other batch location; per-step HIP events over max(steps, 50) steps (median) -------
-    dt_other = None
-    if gstep is not None or cfg == "probe":
-        dt_other = timed(dev_pool if args.host_batches else host_pool, args.steps, 2, first=args.warmup + args.steps)
-    per_step_ms = []
-    n_med = max(args.steps, 50)
-    timed(main_pool, n_med, 2, first=args.warmup + 2 * args.steps + 2, per_step=per_step_ms)
-    per_step_ms.sort()
-    median_ms = per_step_ms[len(per_step_ms) // 2]
-    # ---- roofline leg 2: the same GEMMs alone on the GPU (HIP events around eager launches) -----------------------------------
-    isolated = None
-    L.medp_gemm_profile_enable(1)
-    with torch.no_grad():
-        for i in range(3):
-            teacher.cxr.forward_bf16(dev_pool[0]["pixel_values"]) if cfg != "probe" else probe.encoder.forward_bf16(dev_pool[0]["pixel_values"])
-    torch.cuda.synchronize()
-    abi.check(L.medp_gemm_profile_collect(ctypes.byref(ms), ctypes.byref(n_l), ctypes.byref(fl)), "gemm_profile_collect")
-    L.medp_gemm_profile_enable(0)
-    if n_l.value > 0 and ms.value > 0:
-        isolated = {"achieved": round(fl.value / (ms.value * 1e-3) / 1e12, 1), "launches": int(n_l.value),
-                    "avg_launch_us": round(ms.value * 1e3 / n_l.value, 2)}
+    # ---- side measurements (--full): the other batch location; per-step HIP events over max(steps, 50) steps (median)
+    dt_other = median_ms = n_med = isolated = None
+    if args.full:
+        if gstep is not None or cfg == "probe":
+            dt_other = timed(dev_pool if args.host_batches else host_pool, args.steps, 2, first=args.warmup + args.steps)
+        per_step_ms = []
+        n_med = max(args.steps, 50)
+        timed(main_pool, n_med, 2, first=args.warmup + 2 * args.steps + 2, per_step=per_step_ms)
+        per_step_ms.sort()
+        median_ms = per_step_ms[len(per_step_ms) // 2]
+        # ---- roofline leg 2: the same GEMMs alone on the GPU (HIP events around eager launches) -------------------------------
+        L.medp_gemm_profile_enable(1)
+        with torch.no_grad():
+            for i in range(3):
+                teacher.cxr.forward_bf16(dev_pool[0]["pixel_values"]) if cfg != "probe" else probe.encoder.forward_bf16(dev_pool[0]["pixel_values"])
+        torch.cuda.synchronize()
+        abi.check(L.medp_gemm_profile_collect(ctypes.byref(ms), ctypes.byref(n_l), ctypes.byref(fl)), "gemm_profile_collect")
+        L.medp_gemm_profile_enable(0)
+        if n_l.value > 0 and ms.value > 0:
+            isolated = {"achieved": round(fl.value / (ms.value * 1e-3) / 1e12, 1), "launches": int(n_l.value),
+                        "avg_launch_us": round(ms.value * 1e3 / n_l.value, 2)}
     if rank != 0:
         if torch.distributed.is_initialized():
             torch.distributed.destroy_process_group()
@@ -598,8 +653,9 @@ def main():
            "graph of the next batch beside them on its own stream" if (world > 1 or force_pg) else ""))
     res = {
         "metric": "multimodal train samples/sec", "value": round(value, 2), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "ms_per_step_median": round(median_ms, 3),
-        "ms_per_step_median_of": f"{n_med} steps, HIP events on the step's stream, rank 0", "higher_is_better": True,
+        "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "ms_per_step_median": None if median_ms is None else round(median_ms, 3),
+        "ms_per_step_median_of": None if n_med is None else f"{n_med} steps, HIP events on the step's stream, rank 0", "higher_is_better": True,
         "scaling": "strong" if args.strong else "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
         "config": {"workload": workload, "config": cfg, "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"dp{world}",
                    "batch_location": ("pinned host memory: H2D + feats_to_input inside the timed step" if args.host_batches else
@@ -636,9 +692,9 @@ def main():
             "isolated": isolated,
             "note": "the matrix peak is the nominal roofline; L2 counters (profiles/r01_pmc_tcc_gemm_v6_v7.txt) show the L2 channels 79 % busy "
                     "at 8.1 TB/s of LDS staging traffic: at 128 FLOP per staged byte the binding ceiling is ~1.05 PFLOP/s"}
-        if world == 1 and not args.no_hbm_table and not args.stress:
+        if args.full and world == 1 and not args.no_hbm_table and not args.stress:
             res["roofline"]["hbm_kernels"] = hbm_kernel_table(B, T, V, device, teacher.duett)
-    if world == 1 and not args.no_cpu_baseline and not args.stress and not args.unfreeze_cxr:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.stress and not args.unfreeze_cxr:
         cb = make_batch(ccfg, start=10_000, batch_size=B, mode="teacher")            # the step's own batch ("same B")
         cb1 = make_batch(ccfg, start=20_000, batch_size=min(4, B), mode="teacher")
         res["cpu_baseline"] = cpu_baseline(cfg, trainable, teacher, ccfg, K, cb, cb1)

@@ -11,19 +11,19 @@ cd /tmp
 
 echo "[collect] bench lines"
 for cfg in teacher student probe; do
-  python3 $R/bench.py --config $cfg > $O/${TAG}_bench_$cfg.json 2> $O/${TAG}_bench_$cfg.err
+  python3 $R/bench.py --full --config $cfg > $O/${TAG}_bench_$cfg.json 2> $O/${TAG}_bench_$cfg.err
   tail -c 400 $O/${TAG}_bench_$cfg.json; echo
 done
-python3 $R/bench.py --stress --no-cpu-baseline > $O/${TAG}_bench_stress.json 2> $O/${TAG}_bench_stress.err      # configs[4] shapes at its per-GPU batch (B 32)
+python3 $R/bench.py --full --stress --no-cpu-baseline > $O/${TAG}_bench_stress.json 2> $O/${TAG}_bench_stress.err      # configs[4] shapes at its per-GPU batch (B 32)
 tail -c 400 $O/${TAG}_bench_stress.json; echo
 
 for cfg in teacher student; do
   echo "[collect] kernel trace $cfg"
-  CMD="python3 $R/bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-table"
+  CMD="python3 $R/bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-table"
   rm -rf $O/${TAG}_kt_$cfg
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_kt_$cfg -- $CMD > $O/${TAG}_kt_$cfg.log 2>&1
   {
-    echo "# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-table   ($TAG, final state)"
+    echo "# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-table   ($TAG, final state)"
     echo "# NB: under the profiler the captured graph's branches are serialised (one queue), so this file gives kernel DURATIONS with the"
     echo "#     chip to themselves at profiler clocks, not the overlap; bench.py's in-step clocks (roofline.achieved) are read inside the kernels."
     echo "# bench line of this run: $(grep '^{' $O/${TAG}_kt_$cfg.log | tail -1 | cut -c1-400)"
@@ -39,13 +39,13 @@ for cfg in teacher student; do
 done
 
 echo "[collect] PMC FETCH_SIZE / WRITE_SIZE (separate passes, eager step)"
-PCMD="python3 $R/bench.py --steps 3 --warmup 1 --eager --no-cpu-baseline --no-hbm-table"
+PCMD="python3 $R/bench.py --full --steps 3 --warmup 1 --eager --no-cpu-baseline --no-hbm-table"
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf $O/${TAG}_pmc_$c
   rocprofv3 --pmc $c --output-format csv -d $O/${TAG}_pmc_$c -- $PCMD > $O/${TAG}_pmc_$c.log 2>&1
 done
 {
-  echo "# rocprofv3 --pmc FETCH_SIZE (pass 1) / --pmc WRITE_SIZE (pass 2), no trace domains: python3 bench.py --steps 3 --warmup 1 --eager --no-cpu-baseline --no-hbm-table   ($TAG, final state)"
+  echo "# rocprofv3 --pmc FETCH_SIZE (pass 1) / --pmc WRITE_SIZE (pass 2), no trace domains: python3 bench.py --full --steps 3 --warmup 1 --eager --no-cpu-baseline --no-hbm-table   ($TAG, final state)"
   echo "# columns: dispatches, total KiB, mean KiB per dispatch, kernel   (FETCH_SIZE is doubled in traffic.json as the guide prescribes for gfx950)"
   echo "## FETCH_SIZE"; python3 $R/tools/pmc_summary.py $O/${TAG}_pmc_FETCH_SIZE FETCH_SIZE 24
   echo "## WRITE_SIZE"; python3 $R/tools/pmc_summary.py $O/${TAG}_pmc_WRITE_SIZE WRITE_SIZE 24

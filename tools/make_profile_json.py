@@ -34,7 +34,7 @@ def gemm(trace_dir, bench_file, out, tag):
             line = json.loads(ln)
     doc = {"tag": tag, "kernels": list(GEMMS), "launches": len(allv), "avg_launch_us": round(sum(allv) / max(len(allv), 1), 3),
            "per_kernel_avg_us": {g: round(sum(v) / len(v), 3) for g, v in per.items() if v},
-           "source": f"rocprofv3 --kernel-trace --stats of `python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-table` (profiles/{tag}_kerneltrace_bench_teacher.txt)",
+           "source": f"rocprofv3 --kernel-trace --stats of `python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-hbm-table` (profiles/{tag}_kerneltrace_bench_teacher.txt)",
            "commit": commit(), "date": datetime.date.today().isoformat()}
     if line is not None:
         rf = line["roofline"]
@@ -75,7 +75,7 @@ def traffic(fetch_dir, write_dir, out, tag):
         hist.append({"round": old.get("round"), "fetch_size_kib_raw": old.get("fetch_size_kib_per_launch_raw"),
                      "write_size_kib": old.get("write_size_kib_per_launch"), "bytes_per_launch": old.get("vit_gemm_hbm_bytes_per_launch")})
     doc = {"tag": tag, "round": int(tag[1:3]) if tag[1:3].isdigit() else None, "kernel": " + ".join(GEMMS) + " (CXR-encoder block GEMMs, B=64, 224x224: 4 shapes x 12 layers per step)",
-           "method": "rocprofv3 --pmc FETCH_SIZE and, in a separate pass, --pmc WRITE_SIZE (no trace domains), `bench.py --steps 3 --warmup 1 --eager "
+           "method": "rocprofv3 --pmc FETCH_SIZE and, in a separate pass, --pmc WRITE_SIZE (no trace domains), `bench.py --full --steps 3 --warmup 1 --eager "
                      "--no-cpu-baseline --no-hbm-table` (tools/collect_profiles.sh); mean per dispatch; FETCH_SIZE doubled per "
                      "/opt/skills/guides/MI355X_MICROARCH.md (gfx950 reports half the bytes of a 16-B-per-lane stream; LDS-DMA loads alike); counters in KiB",
            "source": f"profiles/{tag}_pmc_fetch_write_bench_teacher.txt", "commit": commit(), "date": datetime.date.today().isoformat(),
