@@ -39,7 +39,7 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-constexpr int BM = 256, BN = 256, HALF = 128 * 128, KBUF = 4 * HALF;   // 16 KiB half-tile, 64 KiB K-tile buffer
+constexpr int BN = 256, HALF = 128 * 128, KBUF = 4 * HALF;   // 16 KiB half-tile, 64 KiB K-tile buffer
 constexpr int LDS_MAIN = 2 * KBUF, LDS_EPI = 8 * 64 * 68 * 4;
 constexpr int LDS_STATS = LDS_EPI;                         // LayerNorm-fold producer: [256 rows][4 column waves][2] floats behind the epilogue patches
 constexpr int LDS_BYTES = LDS_STATS + 256 * 4 * 2 * 4;
@@ -62,8 +62,15 @@ static_assert(LDS_BYTES >= LDS_MAIN && LDS_BYTES <= 160 * 1024, "v6 LDS plan");
         __builtin_amdgcn_sched_barrier(0);          \
     } while (0)
 
-template <int TAG>
+// GR = tile rows per ping-pong group: 128 (256 x 256 tiles) or 112 (224 x 256 tiles for the N = 768 launches, see launch_v6).
+// With GR = 112 the LDS layout, the DMA piece plan and therefore every vmcnt count stay those of GR = 128: a group's A half
+// still holds 128 rows, rows 112-127 are staged from the zero chunk, and the wave's last 16-row block (i = 3 of a = 1)
+// does no MFMA.  Every output element sees the same MFMAs in the same K order under either GR.
+template <int TAG, int GR>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmArgs p, unsigned* slot) {
+    static_assert(GR == 128 || GR == 112, "v6 group rows");
+    constexpr int BM = 2 * GR;
+    constexpr int NI1 = (GR - 64) / 16;                // 16-row blocks of the wave's second 64-row quadrant (a = 1)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -132,8 +139,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
     for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int ra = m0 + h * 128 + j * 64 + srow, rw = n0 + h * 128 + j * 64 + srow;
-            a_src[h][j] = ra < p.M ? A + (size_t)ra * p.lda + schunk * 8 : nullptr;
+            const int ra = m0 + h * GR + j * 64 + srow, rw = n0 + h * 128 + j * 64 + srow;
+            a_src[h][j] = ((GR == 128 || j * 64 + srow < GR) && ra < p.M) ? A + (size_t)ra * p.lda + schunk * 8 : nullptr;
             w_src[h][j] = rw < p.N ? W + (size_t)rw * p.ldw + schunk * 8 : nullptr;
         }
     // piece j (rows 64 j .. 64 j + 63) of half-tile `which` (0: A rows 0-127, 1: A rows 128-255, 2: W rows 0-127, 3: W rows
@@ -168,7 +175,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
     bf16x8 fa[4][2], fw0a[2][2], fw0b[2][2], fw1[2][2];      // two W0 sets: K-tile t+1's is read while K-tile t's still multiplies
     auto read_a = [&](const char* buf, int a) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < (a == 0 ? 4 : NI1); ++i) {
             const char* rp = buf + fa_off + (a * 64 + i * 16) * 128;
             fa[i][0] = *(const bf16x8*)(rp + ch0);
             fa[i][1] = *(const bf16x8*)(rp + ch1);
@@ -184,14 +191,14 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
     };
     // ragged last row-tile (M = 64 * 257 leaves 64 valid rows of 256): a 64-row quadrant entirely past M keeps its zero
     // accumulators and skips its MFMAs (wave-uniform), so that tile costs its loads and barriers only
-    const bool rows_live[2] = {m0 + wm * 128 < p.M, m0 + wm * 128 + 64 < p.M};
+    const bool rows_live[2] = {m0 + wm * GR < p.M, m0 + wm * GR + 64 < p.M};
     auto mma = [&](int a, int b, const bf16x8 (*fw)[2]) {
         if (!rows_live[a]) return;
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int i = 0; i < (a == 0 ? 4 : NI1); ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
                     acc[a * 4 + i][b * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j][kh], fa[i][kh], acc[a * 4 + i][b * 2 + j], 0, 0, 0);
@@ -259,8 +266,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
     auto load_res = [&](int half) {
 #pragma unroll
         for (int it = 0; it < 16; ++it) {
-            const int m = m0 + wm * 128 + half * 64 + it * 4 + er;
-            res[half][it] = (m < p.M && n < p.N) ? *(const f32x4*)(p.residual + (size_t)m * p.ldr + n) : (f32x4){0.f, 0.f, 0.f, 0.f};
+            const int m = m0 + wm * GR + half * 64 + it * 4 + er;
+            res[half][it] = (half * 64 + it * 4 < GR && m < p.M && n < p.N) ? *(const f32x4*)(p.residual + (size_t)m * p.ldr + n) : (f32x4){0.f, 0.f, 0.f, 0.f};
         }
     };
     const bool has_res = p.residual != nullptr;
@@ -268,7 +275,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
     // LayerNorm fold (gemm_variants.h).  Consumer: the row's mean / rstd from the producer's per-tile partial sums, summed in tile order;
     // C = rstd acc - rstd mean colsum + bias.  Producer: bf16 copy of the fp32 result + this tile's (sum, sum of squares) per row.
     const MedpGemmFold& fo = p.fold;
-    const bool consumer = fo.stats_in != nullptr, producer = fo.c2 != nullptr;
+    const bool consumer = GR == 128 && fo.stats_in != nullptr, producer = GR == 128 && fo.c2 != nullptr;   // (launch_v6: no fold with GR 112)
     f32x4 cs4 = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (consumer && n < p.N) cs4 = *(const f32x4*)(fo.colsum + n);
     const float inv_dim = consumer ? 1.0f / (float)fo.ln_dim : 0.f;
@@ -283,8 +290,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
         if (half == 0 && has_res) load_res(1);      // second half's residual flies while the first half is stored
 #pragma unroll
         for (int it = 0; it < 16; ++it) {
+            if (half * 64 + it * 4 >= GR) continue;   // (compile time) rows of the next tile
             const int rr = it * 4 + er;
-            const int m = m0 + wm * 128 + half * 64 + rr;
+            const int m = m0 + wm * GR + half * 64 + rr;
             f32x4 v = *(const f32x4*)(wl + rr * 68 + ec);
             float s1 = 0.f, s2 = 0.f;
             if (m < p.M && n < p.N) {
@@ -361,11 +369,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
     MEDP_PROF_LEAVE(p.prof, p.prof_flags);
 }
 
-template <int TAG>
-int launch_v6(const MedpGemmArgs& a, hipStream_t stream) {
+template <int TAG, int GR>
+int launch_v6_gr(const MedpGemmArgs& a, hipStream_t stream) {
+    constexpr int BM = 2 * GR;
     const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
     MEDP_ONCE_PER_DEVICE({
-        hipFuncSetAttribute((const void*)gemm_bf16_nt_v6_kernel<TAG>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        hipFuncSetAttribute((const void*)gemm_bf16_nt_v6_kernel<TAG, GR>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     });
     // MEDP_V6_TICKETS=1: one-round grids launch 256 workgroups that queue for the tiles (see the kernel).  OFF by default: the
     // hypothesis it tests — proj / fc2 run 30-40 % slower inside the step because workgroups start late on CUs still holding the
@@ -373,13 +382,26 @@ int launch_v6(const MedpGemmArgs& a, hipStream_t stream) {
     // ticket costs 1.2 us): what the other branch takes from these GEMMs is cache and memory bandwidth, not CU slots.
     static const int tickets_on = [] { const char* e = getenv("MEDP_V6_TICKETS"); return e ? atoi(e) : 0; }();
     unsigned* slot = (tickets_on && tiles >= 64 && tiles < 256) ? medp_gemm_ticket_block(stream) : nullptr;
-    gemm_bf16_nt_v6_kernel<TAG><<<slot ? 256 : tiles, 512, LDS_BYTES, stream>>>(a, slot);
+    gemm_bf16_nt_v6_kernel<TAG, GR><<<slot ? 256 : tiles, 512, LDS_BYTES, stream>>>(a, slot);
     MEDP_LAUNCH_CHECK("medp_gemm_bf16_nt(v6)");
     return 0;
+}
+
+// 224 x 256 tiles (GR = 112) for N = 768 where 256 x 256 tiles leave part of the chip idle: proj / fc2 at M = 64 x 257 are
+// 65 x 3 = 195 tiles of 256 rows on 256 CUs, 74 x 3 = 222 of 224 rows.  Taken for the launches with a residual (proj / fc2)
+// and no LayerNorm fold.  MEDP_V6_N768=0: always 256 x 256 (A/B runs); 2: also the N = 768 launches without a residual.
+bool v6_use_224(const MedpGemmArgs& a) {
+    static const int mode = [] { const char* e = getenv("MEDP_V6_N768"); return e ? atoi(e) : 1; }();
+    const int tiles256 = ((a.M + 255) / 256) * ((a.N + 255) / 256);
+    const int tiles224 = ((a.M + 223) / 224) * ((a.N + 255) / 256);
+    return mode != 0 && a.N == 768 && (a.residual != nullptr || mode == 2) && a.fold.c2 == nullptr && a.fold.stats_in == nullptr &&
+           tiles256 < 256 && tiles224 <= 256;
 }
 
 }  // namespace
 
 int medp_gemm_v6_launch(const MedpGemmArgs& a, int tag, void* stream) {
-    return tag == 1 ? launch_v6<1>(a, (hipStream_t)stream) : launch_v6<0>(a, (hipStream_t)stream);
+    hipStream_t s = (hipStream_t)stream;
+    if (v6_use_224(a)) return tag == 1 ? launch_v6_gr<1, 112>(a, s) : launch_v6_gr<0, 112>(a, s);
+    return tag == 1 ? launch_v6_gr<1, 128>(a, s) : launch_v6_gr<0, 128>(a, s);
 }

@@ -13,7 +13,7 @@ ends = [i for i, r in enumerate(rows) if "adamw_multi_kernel" in r[2]]
 i1 = ends[-3]; i0 = ends[-4] + 1          # a replay in the middle of the timed region
 step = rows[i0:i1 + 1]
 t0 = step[0][0]
-last_vit = max(i for i, r in enumerate(step) if "gemm_bf16_nt_v6_kernel<1>" in r[2] or "layernorm_fwd_reg_kernel<true, 3>" in r[2])
+last_vit = max(i for i, r in enumerate(step) if "gemm_bf16_nt_v6_kernel<1," in r[2] or "layernorm_fwd_reg_kernel<true, 3>" in r[2])
 print(f"step span {(step[-1][1]-t0)/1e3:.1f} us, {len(step)} kernels; CXR encoder ends at {(step[last_vit][1]-t0)/1e3:.1f} us")
 busy = 0
 for s, e, n, q in step[last_vit + 1:]:
