@@ -114,7 +114,8 @@ int medp_attn_bwd_dh64(const void* q, const void* k, const void* v, int ldqkv, c
                        float scale, void* stream);
 /* Small fp32 attention (head dim <= 64, Lk <= 1536), fwd/bwd with optional dropout on the probabilities and
  * optional head-averaged weights (pre-zeroed [B,Lq,Lk]): x_transformers Attention inside the DuETT encoders
- * (model :81,:91) and nn.MultiheadAttention inside _PerceiverBlock (model :759-762, need_weights/average). */
+ * (model :81,:91) and nn.MultiheadAttention inside _PerceiverBlock (model :759-762, need_weights/average).
+ * Few queries over more than 1024 keys: medp_attn_fq_split_* below. */
 int medp_attn_small_fwd(const float* q, int ldq, long long q_batch_stride, const float* k, const float* v, int ldkv,
                         long long kv_batch_stride, void* o, int ldo, int o_bf16, float* attn_avg, int B, int Lq, int Lk,
                         int H, int dh, float scale, float dropout_p, unsigned seed, unsigned stream_id, void* stream);
@@ -122,6 +123,26 @@ int medp_attn_small_bwd(const float* dout, int lddo, const float* q, int ldq, lo
                         const float* v, int ldkv, long long kv_batch_stride, float* dq, int lddq, float* dk, int lddkv,
                         float* dv, int reserved, long long dkv_batch_stride, int B, int Lq, int Lk, int H, int dh, float scale,
                         float dropout_p, unsigned seed, unsigned stream_id, void* stream);
+
+/* Few-query attention over ANY number of keys (head dim 64, 1 <= Lq <= 32, Lk >= 1, fp32): the perceiver's img_cross block on images
+ * above 32 x 32 patches (nn.MultiheadAttention, model :759-762).  The keys are split into slices of 256, one workgroup each; the
+ * slices' partial softmax statistics and sums go to a caller-owned workspace (size from medp_attn_fq_split_ws_bytes, bwd = 0 / 1)
+ * and are merged in a fixed order (no atomics: bitwise reproducible; no allocation: graph-capturable).  Operands as in
+ * medp_attn_small_*: q rows may be shared by the batch (q_batch_stride 0), k / v the two column halves of one [B, Lk(+skip), 2D]
+ * projection, dk / dv a strided view of the same shape; k, v, dk, dv rows 16-byte aligned.  The forward writes o [B, Lq, ldo]
+ * (fp32, or bf16 with o_bf16), lse [B, H, Lq] (natural-log logsumexp of the scaled scores) and, if attn_avg is not null, the head
+ * average of the post-dropout probabilities [B, Lq, Lk] (every element written).  The backward takes o (fp32) and lse from the
+ * forward and writes dq [B, Lq, lddq], dk, dv.  Same dropout stream as medp_attn_small_*. */
+size_t medp_attn_fq_split_ws_bytes(int B, int H, int Lq, int Lk, int bwd);
+int medp_attn_fq_split_fwd(const float* q, int ldq, long long q_batch_stride, const float* k, const float* v, int ldkv,
+                           long long kv_batch_stride, void* o, int ldo, int o_bf16, float* lse, float* attn_avg, float* ws,
+                           size_t ws_bytes, int B, int Lq, int Lk, int H, int dh, float scale, float dropout_p, unsigned seed,
+                           unsigned stream_id, void* stream);
+int medp_attn_fq_split_bwd(const float* dout, int lddo, const float* o, int ldo, const float* lse, const float* q, int ldq,
+                           long long q_batch_stride, const float* k, const float* v, int ldkv, long long kv_batch_stride, float* dq,
+                           int lddq, float* dk, float* dv, int lddkv, long long dkv_batch_stride, float* ws, size_t ws_bytes, int B,
+                           int Lq, int Lk, int H, int dh, float scale, float dropout_p, unsigned seed, unsigned stream_id,
+                           void* stream);
 
 /* ---- normalisation -------------------------------------------------------------------------------- */
 /* nn.LayerNorm (modeling_dinov2.py:348,353 eps 1e-6; model :750-753 eps 1e-5).  y is bf16 (feeds a GEMM) or fp32. */

@@ -80,6 +80,9 @@ SIGNATURES = {
     "medp_attn_bwd_dh64": (I, [P, P, P, I, P, I, P, P, P, P, P, I, I, I, I, F, P]),
     "medp_attn_small_fwd": (I, [P, I, LL, P, P, I, LL, P, I, I, P, I, I, I, I, I, F, F, U, U, P]),
     "medp_attn_small_bwd": (I, [P, I, P, I, LL, P, P, I, LL, P, I, P, I, P, I, LL, I, I, I, I, I, F, F, U, U, P]),
+    "medp_attn_fq_split_ws_bytes": (SZ, [I, I, I, I, I]),
+    "medp_attn_fq_split_fwd": (I, [P, I, LL, P, P, I, LL, P, I, I, P, P, P, SZ, I, I, I, I, I, F, F, U, U, P]),
+    "medp_attn_fq_split_bwd": (I, [P, I, P, I, P, P, I, LL, P, P, I, LL, P, I, P, P, I, LL, P, SZ, I, I, I, I, I, F, F, U, U, P]),
     "medp_layernorm_fwd": (I, [P, I, P, P, P, I, I, P, P, I, I, F, P]),
     "medp_colsum_workspace_bytes": (SZ, [I, I]),
     "medp_layernorm_bwd": (I, [P, I, P, I, P, P, P, P, I, I, P, P, P, I, I, P]),

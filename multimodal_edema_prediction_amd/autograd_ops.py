@@ -5,6 +5,8 @@ bf16 inside `LinearFn` (weights are cached per parameter version), accumulation 
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import functional as Fn
@@ -481,10 +483,23 @@ def dropout_add(y, residual, p, seed, sid):
 
 
 # ---------------------------------------------------------------------------------------------- attention
+def _fq_split_route(kv, skip, Lq, Lk, dh):
+    """Few queries over more than 1024 keys (the perceiver's img_cross above 32 x 32 patches) take the split-key kernels
+    (attention_fq_split.hip); up to 1536 keys MEDP_ATTN_FEWQ=0 or K / V rows that are not 16-byte aligned keep the wave-per-query
+    kernels, which take no more keys."""
+    if dh != 64 or Lq > 32 or Lk <= 1024:
+        return False
+    if Lk > 1536:
+        return True
+    aligned = (kv.data_ptr() + 4 * skip * kv.stride(1)) % 16 == 0 and (kv.stride(0) | kv.stride(1) | kv.shape[-1] // 2) % 4 == 0
+    return aligned and os.environ.get("MEDP_ATTN_FEWQ", "1") != "0"
+
+
 class AttnSmallFn(torch.autograd.Function):
     """Multi-head attention core.  q: [Lq, D] (shared by the batch) or [B, Lq, D]; kv: [B, Lk(+skip), 2D] fused K|V
     projection, of which rows `skip:` are attended (skip=1 drops the CLS row of the image tokens).  Returns
-    ([B, Lq, D], attn_avg or None)."""
+    ([B, Lq, D], attn_avg or None).  Head dim 64 with <= 32 queries over > 1024 keys: the split-key kernels, which also
+    return the rows' logsumexp that their backward consumes (saved with o)."""
 
     @staticmethod
     def forward(ctx, q, kv, H, scale, p, seed, sid, skip, want_avg):
@@ -496,26 +511,36 @@ class AttnSmallFn(torch.autograd.Function):
         dh = D // H
         kview = kv[:, skip:, :D]
         vview = kv[:, skip:, D:]
-        avg = torch.zeros((B, Lq, Lk), dtype=F32, device=kv.device) if want_avg else None
-        o = Fn.attn_small_fwd(q, kview, vview, B, Lq, Lk, H, dh, scale, q_batch_stride=0 if shared else None,
-                              kv_batch_stride=kv.stride(0), dropout_p=p, seed=seed, stream_id=sid, attn_avg=avg)
-        ctx.save_for_backward(q, kv)
-        ctx.cfg = (H, scale, p, seed, sid, skip, shared)
+        split = _fq_split_route(kv, skip, Lq, Lk, dh)
+        if split:
+            o, lse, avg = Fn.attn_fq_split_fwd(q, kview, vview, B, Lq, Lk, H, scale, q_batch_stride=0 if shared else None,
+                                               kv_batch_stride=kv.stride(0), dropout_p=p, seed=seed, stream_id=sid, want_avg=want_avg)
+            ctx.save_for_backward(q, kv, o, lse)
+        else:
+            avg = torch.zeros((B, Lq, Lk), dtype=F32, device=kv.device) if want_avg else None
+            o = Fn.attn_small_fwd(q, kview, vview, B, Lq, Lk, H, dh, scale, q_batch_stride=0 if shared else None,
+                                  kv_batch_stride=kv.stride(0), dropout_p=p, seed=seed, stream_id=sid, attn_avg=avg)
+            ctx.save_for_backward(q, kv)
+        ctx.cfg = (H, scale, p, seed, sid, skip, shared, split)
         if want_avg:
             ctx.mark_non_differentiable(avg)
         return o, avg
 
     @staticmethod
     def backward(ctx, do, _davg):
-        q, kv = ctx.saved_tensors
-        H, scale, p, seed, sid, skip, shared = ctx.cfg
+        H, scale, p, seed, sid, skip, shared, split = ctx.cfg
+        q, kv = ctx.saved_tensors[:2]
         B, Ltot, D2 = kv.shape
         D, Lk = D2 // 2, Ltot - skip
         Lq = q.shape[-2]
         dkv = torch.zeros_like(kv) if skip else torch.empty_like(kv)
-        dq, _, _ = Fn.attn_small_bwd(do.contiguous(), q, kv[:, skip:, :D], kv[:, skip:, D:], B, Lq, Lk, H, D // H, scale,
-                                     q_batch_stride=0 if shared else None, kv_batch_stride=kv.stride(0), dropout_p=p, seed=seed,
-                                     stream_id=sid, dkv_out=dkv[:, skip:, :])
+        kw = dict(q_batch_stride=0 if shared else None, kv_batch_stride=kv.stride(0), dropout_p=p, seed=seed, stream_id=sid,
+                  dkv_out=dkv[:, skip:, :])
+        if split:
+            o, lse = ctx.saved_tensors[2:]
+            dq, _, _ = Fn.attn_fq_split_bwd(do.contiguous(), o, lse, q, kv[:, skip:, :D], kv[:, skip:, D:], B, Lq, Lk, H, scale, **kw)
+        else:
+            dq, _, _ = Fn.attn_small_bwd(do.contiguous(), q, kv[:, skip:, :D], kv[:, skip:, D:], B, Lq, Lk, H, D // H, scale, **kw)
         if shared:
             dq = Fn.colsum(dq.view(B, Lq * D)).view(Lq, D)
         return dq, dkv, None, None, None, None, None, None, None

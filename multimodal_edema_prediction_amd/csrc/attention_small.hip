@@ -2,12 +2,15 @@
 // Used where the attention core is a negligible share of the work and the shapes are MFMA-hostile:
 //   * DuETT event/time encoders: 2 heads, head dim 12, 49 / 97 tokens (x_transformers Encoder, no mask)
 //   * perceiver blocks: 4 heads, head dim 64, 7 pathology queries over 256 patches / 96 hours / 7 latents
+// Head dim 64 with <= 32 queries over more than 1024 keys (img_cross above 448^2) goes to attention_fq_split.hip instead
+// (autograd_ops.AttnSmallFn routes it; MEDP_ATTN_FEWQ=0 keeps <= 1536 keys here, on the wave-per-query kernels).
 // One workgroup per (batch, head); a wave per query row; keys on lanes for QK^T and softmax (wavefront
 // reductions), head-dim on lanes for PV.  Backward recomputes the probabilities, writes dQ per query and
 // accumulates dK/dV in the block's own (batch, head) slice — no cross-block atomics, bitwise reproducible.
 // Dropout on the probabilities uses the counter hash of common.h, regenerated in backward.
 #include <stdlib.h>
 
+#include "attention_fq.h"
 #include "common.h"
 #include "medp_hip.h"
 
@@ -229,40 +232,7 @@ __global__ __launch_bounds__(256) void attn_small_bwd_kernel(const SmallAttnPara
 // KEYS (P V in the forward, dS K in the backward) is a second phase with (16-B column piece, key slice) on the threads — whole
 // 256-B rows per 16 lanes — and a 16-way reduction through LDS.  fp32 throughout; K and V are read once (the backward reads K
 // twice, the second time out of L2), dK / dV rows are written by their key's thread.  Same dropout stream as the kernels above.
-constexpr int FQ = 8;            // most queries
-constexpr int FQ_T = 256;        // threads = keys per chunk
-constexpr int FQ_MAXCH = 4;      // Lk <= 1024
-
-// The compiler would hoist all 8 x 16 broadcast LDS reads of a fully unrolled (d, q) loop nest to the top (512 VGPRs: the backward
-// spilled 8 KB per lane); a compiler + scheduler barrier per d step keeps each step's 8 reads next to their 32 FMAs.
-#define FQ_KEEP_IN_STEP()                    \
-    do {                                     \
-        asm volatile("" ::: "memory");       \
-        __builtin_amdgcn_sched_barrier(0);   \
-    } while (0)
-
-// an LDS address the compiler cannot see through: loads from it can neither be hoisted above this point nor merged with
-// earlier loads of the same bytes (kept in 512 VGPRs from the score phase to the dK phase otherwise)
-__device__ __forceinline__ const float* FQ_OPAQUE(const float* p) {
-    asm volatile("" : "+v"(p));
-    return p;
-}
-
-__device__ __forceinline__ void fq_block_reduce(float (&v)[FQ], float* red, int lane, int wave, bool is_max) {
-#pragma unroll
-    for (int q = 0; q < FQ; ++q) v[q] = is_max ? wave_max(v[q]) : wave_sum(v[q]);
-    __syncthreads();                                   // `red` may still be read from the previous reduction
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < FQ; ++q) red[wave * FQ + q] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < FQ; ++q) {
-        const float a = red[q], b = red[FQ + q], c = red[2 * FQ + q], d = red[3 * FQ + q];
-        v[q] = is_max ? fmaxf(fmaxf(a, b), fmaxf(c, d)) : (a + b) + (c + d);
-    }
-}
+constexpr int FQ_MAXCH = 4;      // Lk <= 1024 (FQ, FQ_T and the shared helpers: attention_fq.h)
 
 // scores of this thread's keys (one per chunk) against all queries; returns the softmax probabilities in pr[ch][q]
 template <int NCH>
@@ -316,39 +286,6 @@ __device__ __forceinline__ void fq_probs(const SmallAttnParams& p, const float* 
     for (int ch = 0; ch < NCH; ++ch)
 #pragma unroll
         for (int q = 0; q < FQ; ++q) pr[ch][q] *= 1.0f / sum[q];
-}
-
-// out[q][0..63] = sum_j w[q][j] * rows[j][0..63]: thread = (16-B piece c of the row, key slice ks of 16); partial sums meet in LDS
-__device__ __forceinline__ void fq_weighted_rows(const float* sW, int ldw, const float* rows, size_t ld, int Lk, int Lq, float* sR, int tid,
-                                                 float* out, size_t ldo) {
-    const int c = tid & 15, ks = tid >> 4;
-    float4 acc[FQ];
-#pragma unroll
-    for (int q = 0; q < FQ; ++q) acc[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int j0 = ks; j0 < Lk; j0 += 16 * 4) {
-        float4 r[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) r[u] = (j0 + 16 * u < Lk) ? *(const float4*)(rows + (size_t)(j0 + 16 * u) * ld + c * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int j = min(j0 + 16 * u, Lk - 1);            // (past the end the row is zero)
-#pragma unroll
-            for (int q = 0; q < FQ; ++q) {
-                const float w = sW[q * ldw + j];
-                acc[q].x += w * r[u].x; acc[q].y += w * r[u].y; acc[q].z += w * r[u].z; acc[q].w += w * r[u].w;
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < FQ; ++q) *(float4*)(sR + ((ks * FQ + q) * 64 + c * 4)) = acc[q];
-    __syncthreads();
-    for (int t = tid; t < Lq * 64; t += FQ_T) {
-        const int q = t >> 6, d = t & 63;
-        float a = 0.f;
-#pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2) a += sR[(k2 * FQ + q) * 64 + d];
-        out[(size_t)q * ldo + d] = a;
-    }
 }
 
 template <int NCH>

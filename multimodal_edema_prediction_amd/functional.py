@@ -265,6 +265,48 @@ def attn_small_bwd(dout, q, k, v, B, Lq, Lk, H, dh, scale, *, q_batch_stride=Non
     return dq, dkv_out[..., :D], dkv_out[..., D:]
 
 
+def attn_fq_split_fwd(q, k, v, B, Lq, Lk, H, scale, *, q_batch_stride=None, kv_batch_stride=None, out_dtype=F32, dropout_p=0.0,
+                      seed=0, stream_id=0, want_avg=False):
+    """Few queries (<= 32) over any number of keys, head dim 64 (key slices of 256 merged in a fixed order).  Operands as in
+    `attn_small_fwd`.  Returns (o [B, Lq, H*64], lse fp32 [B, H, Lq] (natural log), attn_avg [B, Lq, Lk] or None)."""
+    ldq, ldkv = q.stride(-2), k.stride(-2)
+    assert v.stride(-2) == ldkv
+    qbs = Lq * ldq if q_batch_stride is None else q_batch_stride
+    kbs = Lk * ldkv if kv_batch_stride is None else kv_batch_stride
+    o = torch.empty((B, Lq, H * 64), dtype=out_dtype, device=k.device)
+    lse = torch.empty((B, H, Lq), dtype=F32, device=k.device)
+    avg = torch.empty((B, Lq, Lk), dtype=F32, device=k.device) if want_avg else None
+    wsb = lib().medp_attn_fq_split_ws_bytes(B, H, Lq, Lk, 0)
+    ws = torch.empty(wsb // 4, dtype=F32, device=k.device)                 # torch allocator: safe under graph capture
+    check(lib().medp_attn_fq_split_fwd(ptr(q), ldq, qbs, ptr(k), ptr(v), ldkv, kbs, ptr(o), H * 64, int(out_dtype == BF16), ptr(lse),
+                                        ptr(avg), ptr(ws), wsb, B, Lq, Lk, H, 64, scale, dropout_p, seed, stream_id, stream()),
+          "attn_fq_split_fwd")
+    return o, lse, avg
+
+
+def attn_fq_split_bwd(dout, o, lse, q, k, v, B, Lq, Lk, H, scale, *, q_batch_stride=None, kv_batch_stride=None, dropout_p=0.0, seed=0,
+                      stream_id=0, dkv_out=None):
+    """Backward of `attn_fq_split_fwd` from its fp32 o and lse.  Returns (dq [B, Lq, H*64], dk, dv); dk / dv are the column halves of
+    `dkv_out` ([B, Lk, 2*H*64], may be a strided view) as in `attn_small_bwd`."""
+    ldq, ldkv = q.stride(-2), k.stride(-2)
+    qbs = Lq * ldq if q_batch_stride is None else q_batch_stride
+    kbs = Lk * ldkv if kv_batch_stride is None else kv_batch_stride
+    D = H * 64
+    assert o.dtype == F32 and lse.dtype == F32 and lse.is_contiguous()
+    dq = torch.empty((B, Lq, D), dtype=F32, device=k.device)
+    if dkv_out is None:
+        dkv_out = torch.empty((B, Lk, 2 * D), dtype=F32, device=k.device)
+    assert dkv_out.stride(-1) == 1 and dkv_out.shape[-1] == 2 * D
+    d2, o2 = dout.reshape(B * Lq, D), o.reshape(B * Lq, D)
+    wsb = lib().medp_attn_fq_split_ws_bytes(B, H, Lq, Lk, 1)
+    ws = torch.empty(wsb // 4, dtype=F32, device=k.device)
+    base = dkv_out.data_ptr()
+    check(lib().medp_attn_fq_split_bwd(ptr(d2), _ld(d2), ptr(o2), _ld(o2), ptr(lse), ptr(q), ldq, qbs, ptr(k), ptr(v), ldkv, kbs, ptr(dq),
+                                        D, base, base + 4 * D, dkv_out.stride(-2), dkv_out.stride(0), ptr(ws), wsb, B, Lq, Lk, H, 64,
+                                        scale, dropout_p, seed, stream_id, stream()), "attn_fq_split_bwd")
+    return dq, dkv_out[..., :D], dkv_out[..., D:]
+
+
 def gelu_bwd(dy: torch.Tensor, pre: torch.Tensor) -> torch.Tensor:
     dx = torch.empty_like(dy)
     check(lib().medp_gelu_bwd(ptr(dy), ptr(pre), ptr(dx), dy.numel(), stream()), "gelu_bwd")
