@@ -10,8 +10,17 @@ import torch.nn.functional as F
 LN_EPS = 1e-5
 
 
-def mha(q_in, kv_in, sd, p, n_heads, dropout=0.0, training=False, need_weights=False):
-    """`nn.MultiheadAttention(d, h, batch_first=True)(q, k, k)` with packed in_proj."""
+def _dropout(t, p, training, drop, site):
+    """`F.dropout(t, p, training)`, or in training the caller's `drop(t, p, site)`: a hook that applies a known mask (the tests replay
+    the HIP kernels' masks through it).  Without a hook the call and the torch RNG draws are exactly those of the reference."""
+    if drop is None or not training:
+        return F.dropout(t, p, training)
+    return drop(t, p, site)
+
+
+def mha(q_in, kv_in, sd, p, n_heads, dropout=0.0, training=False, need_weights=False, drop=None):
+    """`nn.MultiheadAttention(d, h, batch_first=True)(q, k, k)` with packed in_proj.  `drop`: see `_dropout` (site "attn", the
+    probabilities [B, H, Lq, Lk])."""
     d = q_in.shape[-1]
     W, b = sd[p + "in_proj_weight"], sd[p + "in_proj_bias"]
     q = F.linear(q_in, W[:d], b[:d])
@@ -23,29 +32,30 @@ def mha(q_in, kv_in, sd, p, n_heads, dropout=0.0, training=False, need_weights=F
     sp = lambda t, L: t.view(B, L, n_heads, dh).transpose(1, 2)
     q, k, v = sp(q, Lq), sp(k, Lk), sp(v, Lk)
     w = torch.softmax(torch.matmul(q, k.transpose(-1, -2)) * dh ** -0.5, dim=-1)
-    wd = F.dropout(w, dropout, training)
+    wd = _dropout(w, dropout, training, drop, "attn")
     o = torch.matmul(wd, v).transpose(1, 2).reshape(B, Lq, d)
     o = F.linear(o, sd[p + "out_proj.weight"], sd[p + "out_proj.bias"])
     return o, (wd.mean(dim=1) if need_weights else None)          # average_attn_weights=True
 
 
-def perceiver_block(lat, kv, sd, p, n_heads, dropout=0.0, training=False, return_attn=False):
-    """model file `:759-774`."""
+def perceiver_block(lat, kv, sd, p, n_heads, dropout=0.0, training=False, return_attn=False, drop=None):
+    """model file `:759-774`.  `drop`: see `_dropout`; sites "attn", "ff_gelu" (the GELU output) and "ff_out" (before the residual add)."""
     ln = lambda x, n: F.layer_norm(x, (x.shape[-1],), sd[p + n + ".weight"], sd[p + n + ".bias"], LN_EPS)
     q = ln(lat, "norm_q")
     k = ln(kv, "norm_kv")
-    a, w = mha(q, k, sd, p + "attn.", n_heads, dropout, training, return_attn)
+    a, w = mha(q, k, sd, p + "attn.", n_heads, dropout, training, return_attn, drop)
     lat = lat + a
     h = F.gelu(F.linear(ln(lat, "norm_ff"), sd[p + "ff.0.weight"], sd[p + "ff.0.bias"]))
-    h = F.dropout(h, dropout, training)
-    h = F.dropout(F.linear(h, sd[p + "ff.3.weight"], sd[p + "ff.3.bias"]), dropout, training)
+    h = _dropout(h, dropout, training, drop, "ff_gelu")
+    h = _dropout(F.linear(h, sd[p + "ff.3.weight"], sd[p + "ff.3.bias"]), dropout, training, drop, "ff_out")
     lat = lat + h
     return (lat, w) if return_attn else lat
 
 
 def perceiver_forward(sd, ts_tokens, img_patches_proj, n_heads=4, p="", dropout=0.0, head_dropout=0.0,
-                      training=False, return_attn=False, ts_ablation="hourly_only"):
-    """`PatchDualPathologyPerceiver.forward`, model file `:595-654`."""
+                      training=False, return_attn=False, ts_ablation="hourly_only", drop=None):
+    """`PatchDualPathologyPerceiver.forward`, model file `:595-654`.  `drop`: see `_dropout`; sites "<block>.attn", "<block>.ff_gelu",
+    "<block>.ff_out" of the blocks img_cross, img_self, ts_cross, ts_self, and "image_head", "temporal_head", "correction_head"."""
     if ts_tokens.ndim != 3:
         raise ValueError(f"ts_tokens must be [B, T+1, d_ts], got {tuple(ts_tokens.shape)}")
     B = ts_tokens.size(0)
@@ -60,7 +70,10 @@ def perceiver_forward(sd, ts_tokens, img_patches_proj, n_heads=4, p="", dropout=
         raise ValueError(f"unknown ts_ablation={ts_ablation!r}; expected one of "
                          "{'full', 'hourly_only', 'rep_only'}")
     ts_kv = F.linear(sel, sd[p + "ts_proj.weight"], sd[p + "ts_proj.bias"])
-    blk = lambda lat, kv, name, ra=False: perceiver_block(lat, kv, sd, p + name + ".", n_heads, dropout, training, ra)
+    def blk(lat, kv, name, ra=False):
+        bd = None if drop is None else (lambda t, pr, site: drop(t, pr, name + "." + site))
+        return perceiver_block(lat, kv, sd, p + name + ".", n_heads, dropout, training, ra, bd)
+
     if return_attn:
         I, img_attn = blk(q0, img_patches_proj, "img_cross", True)
     else:
@@ -74,14 +87,14 @@ def perceiver_forward(sd, ts_tokens, img_patches_proj, n_heads=4, p="", dropout=
 
     def head(x, name):
         h = F.gelu(F.linear(x, sd[p + name + ".0.weight"], sd[p + name + ".0.bias"]))
-        h = F.dropout(h, head_dropout, training)
+        h = _dropout(h, head_dropout, training, drop, name)
         return F.linear(h, sd[p + name + ".3.weight"], sd[p + name + ".3.bias"]).squeeze(-1)
 
     img_logits = head(I, "image_head") + sd[p + "image_label_bias"].unsqueeze(0)
     ts_logits = head(T, "temporal_head") + sd[p + "temporal_label_bias"].unsqueeze(0)
     c = F.layer_norm(T, (T.shape[-1],), sd[p + "correction_head.0.weight"], sd[p + "correction_head.0.bias"], LN_EPS)
     c = F.gelu(F.linear(c, sd[p + "correction_head.1.weight"], sd[p + "correction_head.1.bias"]))
-    c = F.dropout(c, head_dropout, training)
+    c = _dropout(c, head_dropout, training, drop, "correction_head")
     ts_correction = F.linear(c, sd[p + "correction_head.4.weight"]).squeeze(-1)
     scaled = sd[p + "beta"].unsqueeze(0) * ts_correction
     fusion = img_logits.detach() + scaled
@@ -93,7 +106,8 @@ def perceiver_forward(sd, ts_tokens, img_patches_proj, n_heads=4, p="", dropout=
 
 
 def teacher_fusion_forward(sd, ts_tokens, img_patches, n_heads=4, **kw):
-    """`TeacherModel.forward` patch-dual branch after the two encoders, model file `:1098-1129`."""
+    """`TeacherModel.forward` patch-dual branch after the two encoders, model file `:1098-1129`.  `kw` goes to `perceiver_forward`
+    (`drop=` included)."""
     proj = F.linear(img_patches, sd["img_proj.weight"], sd["img_proj.bias"])
     out = perceiver_forward(sd, ts_tokens, proj, n_heads, p="perceiver.", **kw)
     res = {"main_logit": out["fusion_logits"][:, 0]}
