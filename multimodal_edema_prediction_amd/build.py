@@ -58,7 +58,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
 def build_variant_lib(tag: str, defines: list) -> str:
     """libmedp_hip_<tag>.so: the library with gemm_bf16_v7.hip compiled with extra -D switches (timing-only ablation builds of the
-    persistent GEMM, tools/ablate_gemm_v7.py: MEDP_V7_ABLATE_MFMA, MEDP_V7_ABLATE_LOADS).  Loaded only through MEDP_HIP_LIB."""
+    persistent GEMM, tools/ablate_gemm_v7.py: MEDP_V7_ABLATE_MFMA, MEDP_V7_ABLATE_LOADS; the phase clocks of build_trace_lib).  Loaded only through MEDP_HIP_LIB."""
     build()
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     src = os.path.join(CSRC, "gemm_bf16_v7.hip")
@@ -75,17 +75,7 @@ def build_variant_lib(tag: str, defines: list) -> str:
 def build_trace_lib() -> str:
     """libmedp_hip_trace.so: the same library with gemm_bf16_v7.hip compiled -DMEDP_V7_PHASE_TRACE (in-kernel phase clocks,
     tools/trace_gemm_v7.py --phases).  A profiling aid, loaded only when MEDP_HIP_LIB points at it."""
-    build()
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    src = os.path.join(CSRC, "gemm_bf16_v7.hip")
-    obj = os.path.join(HERE, "build", "gemm_bf16_v7.trace.o")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
-           "-Wno-unused-result", "-Wno-unused-value", "-DMEDP_V7_PHASE_TRACE", "-c", src, "-o", obj]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    objs = [os.path.join(HERE, "build", os.path.basename(s) + ".o") for s in sources() if not s.endswith("gemm_bf16_v7.hip")] + [obj]
-    out = os.path.join(HERE, "libmedp_hip_trace.so")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs, check=True)
-    return out
+    return build_variant_lib("trace", ["MEDP_V7_PHASE_TRACE"])
 
 
 if __name__ == "__main__":

@@ -180,139 +180,12 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_nt_kernel(const GemmParams p
 
 
 // ------------------------------------------------------------------------------------------------------------------
-// v2: 256 x 128 x 64 tiles, 8 waves (4 x 2, 64 x 64 per wave), THREE LDS slots filled by LDS-DMA two K-tiles ahead.
-// One raw s_barrier per K-tile and a COUNTED s_waitcnt vmcnt (never 0 in the loop), so the loads of tiles t+1 / t+2 stay
-// in flight across the barrier while tile t is multiplied (cdna guide §5 "Pipelining across barriers").
-//   iteration t:  vmcnt(6)  -> tile t landed (this wave's 6 younger loads = tile t+1 may still fly)
-//                 s_barrier -> every wave's tile-t loads landed AND every wave finished reading slot (t-1)%3
-//                 issue tile t+2 into slot (t+2)%3 == (t-1)%3
-//                 ds_read + 32 MFMA on slot t%3
-template <int TAG>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v2_kernel(const GemmParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int BM = 256, BN = 128;
-    constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE = A_BYTES + B_BYTES;   // 48 KiB, x3 = 144 KiB
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fr = lane & 15, kq = lane >> 4;
-    const int wr = wave >> 1, wc = wave & 1;
-
-    const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
-    const int nwg = tiles_m * tiles_n;
-    const int bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    const int m0 = (wg / tiles_n) * BM, n0 = (wg % tiles_n) * BN;
-    const int nkt = (p.K + 63) >> 6;
-    const bf16_t* zero = (const bf16_t*)g_zero16;
-
-    // per-thread source rows are loop-invariant: precompute row base pointers (nullptr -> zero chunk)
-    auto stage = [&](int slot, int kt) {
-        char* sa = smem + slot * STAGE;
-        char* sb = sa + A_BYTES;
-        const int k0 = kt << 6;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int qd = i * 512 + tid;
-            const int row = qd >> 3, c = (qd & 7) ^ (row & 7);
-            const int gr = m0 + row, gk = k0 + c * 8;
-            const bf16_t* src = (gr < p.M && gk < p.K) ? p.A + (size_t)gr * p.lda + gk : zero;
-            glds16(src, sa + (i * 512 + wave * 64) * 16);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int qd = i * 512 + tid;
-            const int row = qd >> 3, c = (qd & 7) ^ (row & 7);
-            const int gr = n0 + row, gk = k0 + c * 8;
-            const bf16_t* src = (gr < p.N && gk < p.K) ? p.W + (size_t)gr * p.ldw + gk : zero;
-            glds16(src, sb + (i * 512 + wave * 64) * 16);
-        }
-    };
-
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    stage(0, 0);
-    if (nkt > 1) stage(1, 1);
-
-    const int a_row0 = wr * 64 + fr, b_row0 = wc * 64 + fr;
-    const int sw = fr & 7;
-    int slot = 0;
-    for (int kt = 0; kt < nkt; ++kt) {
-        if (kt + 1 < nkt) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (kt + 2 < nkt) stage(slot == 0 ? 2 : slot - 1, kt + 2);      // (kt+2)%3 == (slot+2)%3
-        const char* sa = smem + slot * STAGE;
-        const char* sb = sa + A_BYTES;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const int coff = ((s * 4 + kq) ^ sw) << 4;
-            bf16x8 xa[4], wb[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) xa[i] = *(const bf16x8*)(sa + (a_row0 + i * 16) * 128 + coff);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) wb[j] = *(const bf16x8*)(sb + (b_row0 + j * 16) * 128 + coff);
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[j], xa[i], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_s_setprio(0);
-        }
-        slot = slot == 2 ? 0 : slot + 1;
-    }
-
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + wr * 64 + i * 16 + fr;
-        if (m >= p.M) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wc * 64 + j * 16 + kq * 4;
-            if (n >= p.N) continue;
-            f32x4 v = acc[i][j];
-            if (p.bias) v += *(const f32x4*)(p.bias + n);
-            if (p.act == 1) {
-                    v = gelu_erf4(v);
-            }
-            if (p.scale) v *= *(const f32x4*)(p.scale + n);
-            if (p.residual) v += *(const f32x4*)(p.residual + (size_t)m * p.ldr + n);
-            if (p.out_bf16) {
-                uint2 o;
-                o.x = pack_bf2(v[0], v[1]);
-                o.y = pack_bf2(v[2], v[3]);
-                *(uint2*)((bf16_t*)p.C + (size_t)m * p.ldc + n) = o;
-            } else {
-                *(f32x4*)((float*)p.C + (size_t)m * p.ldc + n) = v;
-            }
-        }
-    }
-}
-
-template <int TAG>
-int launch_v2(const GemmParams& p, hipStream_t stream) {
-    const int tiles = ((p.M + 255) / 256) * ((p.N + 127) / 128);
-    constexpr int LDS = 3 * (256 + 128) * 128;
-    MEDP_ONCE_PER_DEVICE({
-        hipFuncSetAttribute((const void*)gemm_bf16_nt_v2_kernel<TAG>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    });
-    gemm_bf16_nt_v2_kernel<TAG><<<tiles, 512, LDS, stream>>>(p);
-    MEDP_LAUNCH_CHECK("medp_gemm_bf16_nt(v2)");
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// v3: the LDS-traffic fix.  v1/v2 give each wave a 64x64 output tile: 32 flop per LDS byte read, and the LDS (fragment
+// v3: the LDS-traffic fix.  v1 gives each wave a 64x64 output tile: 32 flop per LDS byte read, and the LDS (fragment
 // reads + LDS-DMA fills) is as busy as the matrix pipe.  v3 gives each wave 128 x 64 (8 x 4 MFMA tiles, 128 accumulator
 // VGPRs): 43 flop per LDS byte, 12 ds_read_b128 per 32 MFMAs.
 //   block 256 x 128, 4 waves (2 x 2), BK = 32 (64-B LDS rows), THREE 24-KiB slots (72 KiB -> 2 blocks per CU),
-//   LDS-DMA two K-tiles ahead, counted vmcnt + one raw s_barrier per K-tile (same protocol as v2).
+//   LDS-DMA two K-tiles ahead, one raw s_barrier per K-tile and a COUNTED s_waitcnt vmcnt (never 0 in the loop), so the loads of
+//   tiles t+1 / t+2 stay in flight across the barrier while tile t is multiplied.
 //   64-B rows: chunk' = chunk ^ (((row >> 2) & 1) << 1) makes every ds_read_b128 lane group hit 16 distinct 16-B slots.
 template <int TAG>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_nt_v3_kernel(const GemmParams p) {
@@ -694,8 +567,7 @@ static int gemm_dispatch(int tag, const void* A, const void* W, void* C, int M, 
             return N <= 64 ? launch<128, 64, 0>(p, s) : launch<128, 128, 0>(p, s);
         }
     }
-    static const int force = [] { const char* e = getenv("MEDP_GEMM_VARIANT"); return e ? atoi(e) : 0; }();   // 1 = v1, 2 = v2 (A/B tests)
-    const bool use_v2 = force == 2;
+    static const int force = [] { const char* e = getenv("MEDP_GEMM_VARIANT"); return e ? atoi(e) : 0; }();   // 1 = v1, 3 = v3, 6 = v6 (A/B tests)
     // v3 (256 x 128 tiles) only where its grid covers most of the chip: below that the 128 x 128 kernel has twice the tiles
     // (img_proj: 130 -> 258, DuETT ff1 on the time axis: 100 -> 196) and wins on CU fill what it loses per tile
     static const int v3_min_tiles = [] { const char* e = getenv("MEDP_GEMM_V3_MIN_TILES"); return e ? atoi(e) : 192; }();
@@ -741,7 +613,6 @@ static int gemm_dispatch(int tag, const void* A, const void* W, void* C, int M, 
     };
     if (use_v6 && tag != 1) return launch_v67(0);
     if (use_v3 && tag != 1) return launch_v3<0>(p, s);
-    if (use_v2 && tag != 1) return launch_v2<0>(p, s);
     if (tag == 1) {
         const bool prof = g_prof.mode == 1;
         if (g_prof.mode == 2 && use_v6 && g_prof.slot_flops.size() < MAX_PROF_SLOTS) {
@@ -758,7 +629,7 @@ static int gemm_dispatch(int tag, const void* A, const void* W, void* C, int M, 
             }
             hipEventRecord(g_prof.ev[g_prof.used], s);
         }
-        const int rc = use_v6 ? launch_v67(1) : (use_v3 ? launch_v3<1>(p, s) : (use_v2 ? launch_v2<1>(p, s) : launch<128, 128, 1>(p, s)));
+        const int rc = use_v6 ? launch_v67(1) : (use_v3 ? launch_v3<1>(p, s) : launch<128, 128, 1>(p, s));
         if (prof) {
             hipEventRecord(g_prof.ev[g_prof.used + 1], s);
             g_prof.used += 2;

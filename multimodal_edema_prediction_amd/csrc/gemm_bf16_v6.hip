@@ -1,66 +1,17 @@
-// v6: 256 x 256 x 64 tiles, EIGHT waves (2 x 4, 128 x 64 per wave), two waves per SIMD in PING-PONG.
-//
-// v3/v5 measurements: a wave that owns its SIMD alone pays for every LDS-DMA issue (~100+ cycles inside a K-step that also
-// carries the fragment reads) and for every barrier with an idle matrix pipe.  Here each SIMD holds one wave of group 0
-// (rows 0..127 of the tile) and one of group 1 (rows 128..255).  A K-tile (64 deep) is four PHASES of 16 MFMAs (one
-// 64 x 32 quadrant of the wave's 128 x 64 output, both k-halves); every phase is
-//     [load section: ds_read fragments, 2 LDS-DMA pieces, lgkmcnt(0)]  s_barrier  [16 MFMA at raised priority]  s_barrier
-// and group 1 runs ONE barrier behind group 0, so between any two consecutive barriers one group multiplies while the
-// other issues its loads: the matrix pipe always has a wave whose operands are already in registers.
-//
-// LDS: two K-tile buffers of 64 KiB = four 16-KiB half-tiles each (A rows 0-127 | A rows 128-255 | W rows 0-127 |
-// W rows 128-255), 128-B rows, 16-B chunk c stored at c ^ (row & 7) (conflict-free ds_read_b128 lane groups).
-// Fragment schedule of K-tile t (per wave): P1 reads A0 (8) + W0 (4), P2 W1 (4), P3 A1 (8), P4 nothing;
-// MFMA quadrants: P1 (A0,W0)  P2 (A0,W1)  P3 (A1,W1)  P4 (A1,W0).
-// Phase plan of K-tile t (per wave; in-kernel phase clocks, tools/trace_gemm_v7.py --phases, decided it: a load section with
-// 12 ds_read_b128 took 670 ticks against ~330 for the 16 MFMAs it has to hide behind, one with 8 or 4 reads 300-360):
-//     P1: read A rows 0-63 (8),   DMA A rows 64-127 (t+1)   MFMA (A0, W0)
-//     P2: read W1 (4),            DMA A rows 0-63 (t+2)     MFMA (A0, W1)    wait vmcnt(10): A rows 64-127 of K-tile t
-//     P3: read A rows 64-127 (8), DMA W half 0 (t+2)        MFMA (A1, W1)    wait vmcnt(6):  W of K-tile t+1
-//     P4: read W0 of K-TILE t+1 (4) into the other W0 register set,
-//                                 DMA W half 1 (t+2)        MFMA (A1, W0)
-// i.e. no load section carries more than 8 fragment reads or more than 2 DMA pieces (4 pieces + 4 reads in one section cost
-// 560-700 ticks).  Every LDS region is refilled (same buffer) one or two phases after its last read.  The counts of the
-// waits are "everything but the pieces issued after the one needed" (2 pieces per phase, in the order above).
-// RAW: a wait sits in a load section, before a barrier every wave passes, and the data is first read one phase later (group 1
-// runs one barrier behind: a wait placed after the MFMAs would not yet have been executed by it).  WAR: every ds_read is
-// retired (lgkmcnt(0)) before the barrier that ends its load section; the refill is issued one phase later.
+// v6: the 256 x 256 x 64 ping-pong K-loop of gemm_tile256.h (tile map, phase plan and counted waits are described there), ONE tile
+// per workgroup, for every epilogue: bias / GELU / LayerScale / fp32 residual, fp32 or bf16 result, both sides of the LayerNorm fold.
 #include <stdlib.h>
 
 #include "common.h"
+#include "gemm_tile256.h"
 #include "gemm_variants.h"
 
 namespace {
 
-__device__ __attribute__((aligned(16))) uint32_t g_zero16_v6[4] = {0, 0, 0, 0};
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-constexpr int BN = 256, HALF = 128 * 128, KBUF = 4 * HALF;   // 16 KiB half-tile, 64 KiB K-tile buffer
 constexpr int LDS_MAIN = 2 * KBUF, LDS_EPI = 8 * 64 * 68 * 4;
 constexpr int LDS_STATS = LDS_EPI;                         // LayerNorm-fold producer: [256 rows][4 column waves][2] floats behind the epilogue patches
 constexpr int LDS_BYTES = LDS_STATS + 256 * 4 * 2 * 4;
 static_assert(LDS_BYTES >= LDS_MAIN && LDS_BYTES <= 160 * 1024, "v6 LDS plan");
-
-// patch write -> read (and read -> next write) inside ONE wave: the LDS executes a wave's operations in order, only the
-// compiler must not reorder them.  (A workgroup-scope fence here also emits vmcnt(0): the second half of the epilogue would
-// wait for the global stores of the first.)
-#define MEDP_WAVE_LDS_SYNC()                        \
-    do {                                            \
-        asm volatile("" ::: "memory");              \
-        __builtin_amdgcn_wave_barrier();            \
-        asm volatile("" ::: "memory");              \
-    } while (0)
-
-#define MEDP_BAR()                                  \
-    do {                                            \
-        __builtin_amdgcn_sched_barrier(0);          \
-        __builtin_amdgcn_s_barrier();               \
-        __builtin_amdgcn_sched_barrier(0);          \
-    } while (0)
 
 // GR = tile rows per ping-pong group: 128 (256 x 256 tiles) or 112 (224 x 256 tiles for the N = 768 launches, see launch_v6).
 // With GR = 112 the LDS layout, the DMA piece plan and therefore every vmcnt count stay those of GR = 128: a group's A half
@@ -78,10 +29,11 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
     const int wm = wave >> 2, wn = wave & 3;          // wm = ping-pong group
     const bf16_t* A = (const bf16_t*)p.A;
     const bf16_t* W = (const bf16_t*)p.W;
-    const bf16_t* zero = (const bf16_t*)g_zero16_v6;
+    const bf16_t* zero = (const bf16_t*)g_zero16_t256;
     MEDP_PROF_ENTER(p.prof, p.prof_flags);
 
-    const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
+    const Tile256Map map(p.M, p.N, BM);
+    const int tiles_n = map.tiles_n;
     // Tile index.  Static: workgroup b owns tile b.  With a ticket block (`slot`, one-round grids inside a multi-stream step: proj /
     // fc2, 195 tiles) MORE workgroups than tiles are launched and each draws its tile from the queue of its XCD (ticket t of XCD x
     // is tile 8 t + x: the tile the static map gives that XCD's t-th workgroup, so the L2 locality of the map below holds): the
@@ -96,7 +48,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
         __syncthreads();
         bid = 8 * (int)__builtin_amdgcn_readfirstlane(box[0]) + xcd;
         __syncthreads();                                   // everyone has read the ticket before the first LDS-DMA piece may land on it
-        if (bid >= tiles_m * tiles_n) {
+        if (bid >= map.tiles_m * tiles_n) {
             if (tid == 0) {                                // the last workgroup to leave re-arms the ticket block (as in gemm_bf16_v7.hip)
                 const unsigned left = __hip_atomic_fetch_add(slot + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (left == gridDim.x - 1)
@@ -106,29 +58,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
             return;
         }
     }
-    // Block -> tile.  Workgroups are dispatched in index order, block b to XCD b % 8, one per CU (32 CUs per XCD).  The
-    // FULL row-tiles come first: XCD x gets a contiguous run of them (band x super-column order inside, see v3) so its L2 sees
-    // few panels; the cheap tiles of a ragged last row (M = 64 * 257: 64 live rows, three quarters of their MFMAs skipped)
-    // take the highest indices, i.e. they are dispatched LAST.  fc1 (768 full + 12 ragged tiles) is then 96 full tiles =
-    // exactly 3 rounds per XCD plus a short ragged tail, instead of a fourth round that holds one full tile per XCD.
-    const int rag = (p.M % BM) ? 1 : 0;
-    const int tm_full = tiles_m - rag;
-    const int nfull = tm_full * tiles_n;
-    const int full8 = nfull & ~7;                      // full tiles dealt in runs of nfull/8 per XCD; the rest by index
     int m0, n0;
-    if (bid < nfull) {
-        const int wg = bid < full8 ? (bid & 7) * (full8 >> 3) + (bid >> 3) : bid;   // the < 8 leftover full tiles keep their index
-        constexpr int MB = 8, SN = 4;
-        const int band = wg / (MB * tiles_n), rb = wg % (MB * tiles_n);
-        const int mb = min(MB, tm_full - band * MB);
-        const int sc = rb / (mb * SN), r2 = rb % (mb * SN);
-        const int sn = min(SN, tiles_n - sc * SN);
-        m0 = (band * MB + r2 / sn) * BM;
-        n0 = (sc * SN + r2 % sn) * BN;
-    } else {                                           // the ragged row, one tile per column
-        m0 = tm_full * BM;
-        n0 = (bid - nfull) * BN;
-    }
+    map.origin(bid, 8, 4, BM, m0, n0);          // bands of 8 row-tiles x super-columns of 4 column-tiles = one round of an XCD's 32 CUs
     const int nkt = (p.K + 63) >> 6;
 
     // ---- LDS-DMA staging: half-tile = 128 rows x 8 chunks; lane's two pieces are rows (tid>>3) and (tid>>3)+64 ------
@@ -146,7 +77,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
     // piece j (rows 64 j .. 64 j + 63) of half-tile `which` (0: A rows 0-127, 1: A rows 128-255, 2: W rows 0-127, 3: W rows
     // 128-255) of K-tile kt -> buffer kt & 1; past K (the tail of the stream) the source is the zero chunk, counts stay uniform
     auto stage_piece = [&](int kt, int which, int j) {
-        char* dst = smem + (kt & 1) * KBUF + which * HALF + wave * 1024 + j * 8192;
+        char* dst = piece_dst(smem, kt & 1, which, wave, j);
         const int k0 = kt * 64;
         const bool kin = k0 + schunk * 8 < p.K;
         const bf16_t* base = which < 2 ? a_src[which & 1][j] : w_src[which & 1][j];
@@ -161,7 +92,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    // prologue: K-tiles 0 and 1, in the order of the steady-state stream
+    // prologue: K-tiles 0 and 1, in the order of the steady-state stream (gemm_tile256.h)
     stage_a(0, 0); stage_w(0, 0); stage_w(0, 1); stage_a(0, 1);
     stage_a(1, 0); stage_w(1, 0); stage_w(1, 1);           // (A rows 64-127 of K-tile 1 follow in P1 of K-tile 0)
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");       // A rows 0-63 and W of K-tile 0
@@ -209,38 +140,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
     read_w(smem, 0, fw0a);
     if (wm == 1) MEDP_BAR();       // group 1 runs one barrier behind (group 0 pays its extra barrier after the loop)
 
+    auto none = [](int) {};
     auto ktile = [&](int kt, const bf16x8 (*fw0)[2], bf16x8 (*fw0n)[2]) {
-        const char* buf = smem + (kt & 1) * KBUF;
-        // ---- P1
-        read_a(buf, 0);
-        stage_a(kt + 1, 1);
-        __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0), vmcnt/expcnt untouched
-        MEDP_BAR();
-        mma(0, 0, fw0);
-        MEDP_BAR();
-        // ---- P2
-        read_w(buf, 1, fw1);
-        stage_a(kt + 2, 0);
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        asm volatile("s_waitcnt vmcnt(10)" ::: "memory");   // A rows 64-127 of K-tile kt (issued in P1(kt-1)) have landed
-        MEDP_BAR();
-        mma(0, 1, fw1);
-        MEDP_BAR();
-        // ---- P3
-        read_a(buf, 1);
-        stage_w(kt + 2, 0);
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");    // W (and A rows 0-63) of K-tile kt+1 (issued in P2..P4(kt-1)) have landed
-        MEDP_BAR();
-        mma(1, 1, fw1);
-        MEDP_BAR();
-        // ---- P4
-        read_w(smem + ((kt + 1) & 1) * KBUF, 0, fw0n);
-        stage_w(kt + 2, 1);
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        MEDP_BAR();
-        mma(1, 0, fw0);
-        MEDP_BAR();
+        tile256_ktile<false>(smem, kt, fw0, fw0n, fw1, read_a, read_w, mma, stage_a, stage_w, none, none);
     };
     for (int kt = 0; kt < nkt; kt += 2) {
         ktile(kt, fw0a, fw0b);

@@ -1,4 +1,4 @@
-// v7: the v6 K-loop (256 x 256 x 64 tiles, 8 waves, two ping-pong groups, see gemm_bf16_v6.hip) made PERSISTENT for grids of
+// v7: the 256 x 256 x 64 ping-pong K-loop of gemm_tile256.h (the one gemm_bf16_v6.hip runs once per workgroup) made PERSISTENT for grids of
 // more than one round of workgroups with a bf16 result and no residual (qkv: 585 tiles, fc1: 780 tiles on 256 CUs).
 //
 // 256 workgroups (MEDP_V7_WGS) stay resident and walk the tile list:
@@ -23,22 +23,16 @@
 #include <atomic>
 
 #include "common.h"
+#include "gemm_tile256.h"
 #include "gemm_variants.h"
 
 namespace {
-
-__device__ __attribute__((aligned(16))) uint32_t g_zero16_v7[4] = {0, 0, 0, 0};
 
 constexpr int SLOT_WORDS = 16;                    // 8 per-XCD ticket counters, 1 exit counter, padding (64 B)
 constexpr int RING_SLOTS = 1024, CAPTURE_SLOTS = 15360;
 __device__ unsigned g_v7_slots[(RING_SLOTS + CAPTURE_SLOTS) * SLOT_WORDS];   // zero at module load, self-resetting
 
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-constexpr int BM = 256, BN = 256, HALF = 128 * 128, KBUF = 4 * HALF;   // 16 KiB half-tile, 64 KiB K-tile buffer
+constexpr int BM = 256;
 constexpr int PROW = 144;                                              // bytes per patch row: 64 bf16 + 16 B pad (b128 reads stay aligned)
 constexpr int PATCH = 16 * PROW;                                       // one wave's 16 x 64 bf16 patch
 constexpr int MAILBOX = 2 * KBUF + 8 * PATCH;                          // the next tile index, written by wave 0
@@ -49,23 +43,6 @@ constexpr int CSBUF = STATBUF + 256 * 4 * 2 * 4;                       // 2 x 25
 constexpr int LDS_BYTES = CSBUF + 2048;
 static_assert(LDS_BYTES <= 160 * 1024, "K buffers + patches + mailbox exceed the LDS");
 constexpr int NWG = 256;                                               // resident workgroups = CUs of an MI355X
-
-// patch write -> read (and read -> next write) inside ONE wave: the LDS executes a wave's operations in order, only the
-// compiler must not reorder them.  (A workgroup-scope fence here also emits vmcnt(0): every pass would wait for the global
-// stores of the pass before.)
-#define MEDP_WAVE_LDS_SYNC()                        \
-    do {                                            \
-        asm volatile("" ::: "memory");              \
-        __builtin_amdgcn_wave_barrier();            \
-        asm volatile("" ::: "memory");              \
-    } while (0)
-
-#define MEDP_BAR()                                  \
-    do {                                            \
-        __builtin_amdgcn_sched_barrier(0);          \
-        __builtin_amdgcn_s_barrier();               \
-        __builtin_amdgcn_sched_barrier(0);          \
-    } while (0)
 
 // -DMEDP_V7_PHASE_TRACE (tools/build_trace_lib.sh, a separate library): every wave sums, per K-tile phase, the clock ticks
 // of {load section, wait at its barrier, MFMA issue, wait at its barrier}; dumped behind the tile timeline.
@@ -91,35 +68,16 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v7_kernel(const MedpGemmA
     const int wm = wave >> 2, wn = wave & 3;          // wm = ping-pong group
     const bf16_t* A = (const bf16_t*)p.A;
     const bf16_t* W = (const bf16_t*)p.W;
-    const bf16_t* zero = (const bf16_t*)g_zero16_v7;
+    const bf16_t* zero = (const bf16_t*)g_zero16_t256;
     MEDP_PROF_ENTER(p.prof, p.prof_flags);
 
-    const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
-    const int ntiles = tiles_m * tiles_n;
-    const int rag = (p.M % BM) ? 1 : 0;
-    const int tm_full = tiles_m - rag;
-    const int nfull = tm_full * tiles_n;
-    const int full8 = nfull & ~7;
-    // tile index -> origin: the v6 map (full row-tiles in XCD-contiguous band x super-column order, the ragged row last)
-    auto origin = [&](int bid, int& m0, int& n0) {
-        if (bid < nfull) {
-            const int wg = bid < full8 ? (bid & 7) * (full8 >> 3) + (bid >> 3) : bid;
-            const int band = wg / (MB * tiles_n), rb = wg % (MB * tiles_n);
-            const int mb = min(MB, tm_full - band * MB);
-            const int sc = rb / (mb * SN), r2 = rb % (mb * SN);
-            const int sn = min(SN, tiles_n - sc * SN);
-            m0 = (band * MB + r2 / sn) * BM;
-            n0 = (sc * SN + r2 % sn) * BN;
-        } else {
-            m0 = tm_full * BM;
-            n0 = (bid - nfull) * BN;
-        }
-    };
+    const Tile256Map map(p.M, p.N, BM);
+    const int ntiles = map.tiles_m * map.tiles_n;
     const int nkt = p.K >> 6;                          // host guarantees K % 128 == 0 and K >= 256: nkt even, >= 4
     const int xcd = blockIdx.x & 7;
 
     int m0, n0;
-    origin(blockIdx.x, m0, n0);
+    map.origin(blockIdx.x, MB, SN, BM, m0, n0);
 
     // ---- LDS-DMA staging: half-tile = 128 rows x 8 chunks; lane's two pieces are rows (tid>>3) and (tid>>3)+64 ------
     const int srow = tid >> 3, schunk = (tid & 7) ^ (srow & 7);       // source chunk for LDS position (tid & 7)
@@ -144,7 +102,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v7_kernel(const MedpGemmA
 #ifdef MEDP_V7_ABLATE_LOADS      // timing-only build (tools/ablate_gemm_v7.py): the K-loop without its staging stream (wrong results)
         if (ablate_on) return;
 #endif
-        char* dst = smem + b * KBUF + which * HALF + wave * 1024 + j * 8192;
+        char* dst = piece_dst(smem, b, which, wave, j);
         const bool kin = k0 + schunk * 8 < p.K;
         const int r = (which < 2 ? m_src : n_src) + (which & 1) * 128 + j * 64 + srow;
         const bool ok = kin && r < (which < 2 ? p.M : p.N);
@@ -303,68 +261,28 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v7_kernel(const MedpGemmA
         pt_last = (unsigned)__builtin_readcyclecounter();
 #endif
         int t_next = -1, m0n = 0, n0n = 0;
-        // one K-tile; the phase plan and the waits are those of gemm_bf16_v6.hip.  The stream runs two K-tiles ahead and from
-        // K-tile nkt-2 on belongs to the NEXT tile (its K-tiles 0 and 1; nobody: zero source): when the loop ends all of them but
-        // the last A piece are issued, and the W0 fragments of the next K-tile 0 are in registers.  Tiles start with those
-        // landed, so the waits of K-tile 0 are skipped: the first wait that covers the previous tile's output stores is P2 of
-        // K-tile 1.
-        auto ktile = [&](int kt, const bf16x8 (*fw0)[2], bf16x8 (*fw0n)[2]) {
-            const char* buf = smem + (kt & 1) * KBUF;
-            const int k2 = kt + 2 < nkt ? (kt + 2) * 64 : (kt + 2 - nkt) * 64;
-            const int k1 = kt + 1 < nkt ? (kt + 1) * 64 : 0;
-            const int b2 = kt & 1;
-            // ---- P1
-            read_a(buf, 0);
-            stage_a(k1, b2 ^ 1, 1);
-            __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0), vmcnt/expcnt untouched
-            PT(0);
-            MEDP_BAR();
-            PT(1);
-            mma(0, 0, fw0);
-            PT(2);
-            MEDP_BAR();
-            PT(3);
-            // ---- P2
-            if (kt == nkt - 2) {       // from here on the stream reads the next tile (P1 above still staged this tile's last A piece)
+        // The K-tile body is the shared one (gemm_tile256.h).  The stream runs two K-tiles ahead and from K-tile nkt-2 on belongs
+        // to the NEXT tile (its K-tiles 0 and 1; nobody: zero source): when the loop ends all of them but the last A piece are
+        // issued, and the W0 fragments of the next K-tile 0 are in registers.  Tiles start with those landed, so the waits of
+        // K-tile 0 are skipped: the first wait that covers the previous tile's output stores is P2 of K-tile 1.
+        auto before_p2 = [&](int kt) {
+            if (kt == nkt - 2) {       // from here on the stream reads the next tile (P1 still staged this tile's last A piece)
                 t_next = __builtin_amdgcn_readfirstlane(mailbox[0]);
-                if (t_next >= 0) origin(t_next, m0n, n0n);
+                if (t_next >= 0) map.origin(t_next, MB, SN, BM, m0n, n0n);
                 set_m(t_next >= 0 ? m0n : NOBODY);
                 set_n(t_next >= 0 ? n0n : NOBODY);
             }
-            read_w(buf, 1, fw1);
-            stage_a(k2, b2, 0);
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            if (kt >= 1) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");   // A rows 64-127 of K-tile kt (issued in P1(kt-1)) have landed
-            PT(4);
-            MEDP_BAR();
-            PT(5);
-            mma(0, 1, fw1);
-            PT(6);
-            MEDP_BAR();
-            PT(7);
-            // ---- P3
-            read_a(buf, 1);
-            stage_w(k2, b2, 0);
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            if (kt >= 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");    // W (and A rows 0-63) of K-tile kt+1 have landed
-            PT(8);
-            MEDP_BAR();
-            PT(9);
-            mma(1, 1, fw1);
-            PT(10);
-            MEDP_BAR();
-            PT(11);
-            // ---- P4
-            read_w(smem + ((kt + 1) & 1) * KBUF, 0, fw0n);
-            stage_w(k2, b2, 1);
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            PT(12);
-            MEDP_BAR();
-            PT(13);
-            mma(1, 0, fw0);
-            PT(14);
-            MEDP_BAR();
-            PT(15);
+        };
+        auto clock = [&](int k) { PT(k); };
+        auto ktile = [&](int kt, const bf16x8 (*fw0)[2], bf16x8 (*fw0n)[2]) {
+            // where K-tiles kt + 1 and kt + 2 of the stream live: element offset in the source tile and K buffer (computed here, at the
+            // top of the K-tile, and not inside the stream lambdas: that keeps the compiler's code the one the waits were measured with)
+            const int k2 = kt + 2 < nkt ? (kt + 2) * 64 : (kt + 2 - nkt) * 64;
+            const int k1 = kt + 1 < nkt ? (kt + 1) * 64 : 0;
+            const int b2 = kt & 1;
+            auto stream_a = [&](int t, int j) { if (t == kt + 1) stage_a(k1, b2 ^ 1, j); else stage_a(k2, b2, j); };
+            auto stream_w = [&](int, int h) { stage_w(k2, b2, h); };
+            tile256_ktile<true>(smem, kt, fw0, fw0n, fw1, read_a, read_w, mma, stream_a, stream_w, before_p2, clock);
         };
 #pragma clang loop unroll(disable)
         for (int kt = 0; kt < nkt; kt += 2) {

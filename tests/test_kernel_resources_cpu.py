@@ -1,6 +1,8 @@
 """Kernels whose `s_waitcnt vmcnt(N)` waits are counted by hand (the LDS-DMA pieces and loads of a phase, in issue order) must keep
 every value in registers: a VGPR spill adds scratch loads and stores to the vector-memory counter and silently shifts those counts.
-Compiles the sources for gfx950 with the resource-usage remarks and fails on any scratch or VGPR spill in those kernels."""
+Compiles the sources for gfx950 with the resource-usage remarks and fails on any scratch or VGPR spill in those kernels.
+The counted K-tile body of the two 256-tile GEMMs is written once, in csrc/gemm_tile256.h (tile256_ktile); it is compiled into the kernels of
+gemm_bf16_v6.hip and gemm_bf16_v7.hip, which are what is checked here."""
 import os
 import re
 import shutil
@@ -13,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "multimodal_edema_prediction_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-# source -> the kernels in it with hand-counted vmcnt waits (a substring of the mangled name)
+# source -> the kernels in it with hand-counted vmcnt waits (a substring of the mangled name); the waits of the two GEMMs live in gemm_tile256.h
 HAND_COUNTED = {
     "gemm_bf16_v6.hip": ["gemm_bf16_nt_v6_kernel"],
     "gemm_bf16_v7.hip": ["gemm_bf16_nt_v7_kernel"],

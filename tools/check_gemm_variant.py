@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Correctness screen for the GEMM variant selected by MEDP_GEMM_VARIANT (big-M path): ragged M/N/K, all epilogues, repeated
+"""Correctness screen for the GEMM variant selected by MEDP_GEMM_VARIANT (1 = 128-tile kernel, 3 = v3, 6 = v6; big-M path): ragged M/N/K, all epilogues, repeated
 runs (a staging race shows up as rare wrong tiles), against an fp32 torch product of the same bf16 operands."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
