@@ -123,6 +123,21 @@ int medp_attn_small_bwd(const float* dout, int lddo, const float* q, int ldq, lo
                         const float* v, int ldkv, long long kv_batch_stride, float* dq, int lddq, float* dk, int lddkv,
                         float* dv, int reserved, long long dkv_batch_stride, int B, int Lq, int Lk, int H, int dh, float scale,
                         float dropout_p, unsigned seed, unsigned stream_id, void* stream);
+/* The same with a key-padding mask (nn.MultiheadAttention(key_padding_mask=...); analysis/train_trajectory_probe.py:156-163):
+ * key_mask [B, Lk] bytes (rows mask_batch_stride apart), non-zero = key ignored: score -inf, probability exactly 0.  The dropout
+ * stream is indexed over the full Lk as above (same seed: same mask on the surviving keys).  attn_avg, if not null, need not be
+ * zeroed: every element is written once, heads added in a fixed order (bitwise reproducible), masked keys exactly 0.  The backward
+ * writes exact zeros to the dk / dv rows of masked keys.  A batch element whose keys are all masked gives zero probabilities, output
+ * and gradients.  Always the wave-per-query kernels (the few-query and split-key kernels take no mask). */
+int medp_attn_small_masked_fwd(const float* q, int ldq, long long q_batch_stride, const float* k, const float* v, int ldkv,
+                               long long kv_batch_stride, void* o, int ldo, int o_bf16, float* attn_avg, int B, int Lq, int Lk,
+                               int H, int dh, float scale, float dropout_p, unsigned seed, unsigned stream_id, void* stream,
+                               const unsigned char* key_mask, long long mask_batch_stride);
+int medp_attn_small_masked_bwd(const float* dout, int lddo, const float* q, int ldq, long long q_batch_stride, const float* k,
+                               const float* v, int ldkv, long long kv_batch_stride, float* dq, int lddq, float* dk, int lddkv,
+                               float* dv, int reserved, long long dkv_batch_stride, int B, int Lq, int Lk, int H, int dh, float scale,
+                               float dropout_p, unsigned seed, unsigned stream_id, void* stream, const unsigned char* key_mask,
+                               long long mask_batch_stride);
 
 /* Few-query attention over ANY number of keys (head dim 64, 1 <= Lq <= 32, Lk >= 1, fp32): the perceiver's img_cross block on images
  * above 32 x 32 patches (nn.MultiheadAttention, model :759-762).  The keys are split into slices of 256, one workgroup each; the
@@ -373,6 +388,16 @@ int medp_adamw_chunk_elems(void);   /* elements one workgroup updates; block b h
 /* step: host step count (>= 1), used when dev_step == NULL; dev_step: device counter holding the step (graph replay) */
 int medp_adamw_multi(const MedpAdamTensor* dev_descs, const int* dev_block_tensor, const int* dev_block_chunk, int n_blocks,
                      float beta1, float beta2, float eps, int step, const unsigned* dev_step, float grad_scale, void* stream);
+/* Global-norm gradient clipping on the device (torch.nn.utils.clip_grad_norm_, error_if_nonfinite=False; the gradients themselves
+ * are not rewritten).  medp_grad_sumsq_multi: over the same table and block map, workgroup b writes its chunk's sum of squares to
+ * dev_partials[b] (n_blocks floats, caller-owned); a single workgroup then adds them in index order (no atomics: bitwise
+ * reproducible) and writes dev_out[0] = norm, dev_out[1] = min(1, max_norm / (norm + 1e-6)).  medp_adamw_multi_dscale is
+ * medp_adamw_multi with the gradient scale read from device memory (dev_out + 1), so the clip can sit inside a captured step. */
+int medp_grad_sumsq_multi(const MedpAdamTensor* dev_descs, const int* dev_block_tensor, const int* dev_block_chunk, int n_blocks,
+                          float* dev_partials, float max_norm, float* dev_out, void* stream);
+int medp_adamw_multi_dscale(const MedpAdamTensor* dev_descs, const int* dev_block_tensor, const int* dev_block_chunk, int n_blocks,
+                            float beta1, float beta2, float eps, int step, const unsigned* dev_step, const float* dev_grad_scale,
+                            void* stream);
 
 /* ---- HIP-graph support: state that must change between replays lives in device memory --------------------------------
  * medp_rng_set_epoch_ptr: device uint32 mixed into every dropout seed (NULL = off); medp_counter_advance: *c += 1 */
@@ -441,10 +466,14 @@ int medp_add_bcast(const float* a, const float* b, float* out, long long per_bat
  *   (r | z | n) and hn [S,T,d] (= W_hn h + b_hn) are saved for the backward (both null: inference).
  * medp_gru_bwd: dh [S,T,d] (gradient w.r.t. every h_t) -> dgi [S,T,3d], dghn [S,T,d] (gradient w.r.t. W_hn h + b_hn) and
  *   dgh_bf16 [S,T,3d] (r | z | n parts of the gradient w.r.t. h W_hh^T + b_hh; dW_hh = dgh^T h_prev is a medp_gemm_bf16_tn).
- *   whh_t_bf16 [d,3d] = W_hh transposed. */
+ *   whh_t_bf16 [d,3d] = W_hh transposed.
+ * medp_gru_fwd_f32: the forward with fp32 weights, fp32 products and libm exp / tanh (the fp32 kernel mode: a parity instrument);
+ *   whh_t [d, ld_whh_t >= 3d] fp32 = W_hh transposed; same outputs, so medp_gru_bwd serves it too. */
 int medp_traj_features(const float* x, float* out, int B, int T, int V, void* stream);
 int medp_gru_fwd(const float* gi, const void* whh_bf16, const float* bhh, float* hseq, float* gates, float* hn, int S, int T, int d,
                  void* stream);
+int medp_gru_fwd_f32(const float* gi, const float* whh_t, int ld_whh_t, const float* bhh, float* hseq, float* gates, float* hn, int S,
+                     int T, int d, void* stream);
 int medp_gru_bwd(const float* dh, const float* gates, const float* hn, const float* hseq, const void* whh_t_bf16, float* dgi,
                  float* dghn, void* dgh_bf16, int S, int T, int d, void* stream);
 

@@ -80,6 +80,8 @@ SIGNATURES = {
     "medp_attn_bwd_dh64": (I, [P, P, P, I, P, I, P, P, P, P, P, I, I, I, I, F, P]),
     "medp_attn_small_fwd": (I, [P, I, LL, P, P, I, LL, P, I, I, P, I, I, I, I, I, F, F, U, U, P]),
     "medp_attn_small_bwd": (I, [P, I, P, I, LL, P, P, I, LL, P, I, P, I, P, I, LL, I, I, I, I, I, F, F, U, U, P]),
+    "medp_attn_small_masked_fwd": (I, [P, I, LL, P, P, I, LL, P, I, I, P, I, I, I, I, I, F, F, U, U, P, P, LL]),
+    "medp_attn_small_masked_bwd": (I, [P, I, P, I, LL, P, P, I, LL, P, I, P, I, P, I, LL, I, I, I, I, I, F, F, U, U, P, P, LL]),
     "medp_attn_fq_split_ws_bytes": (SZ, [I, I, I, I, I]),
     "medp_attn_fq_split_fwd": (I, [P, I, LL, P, P, I, LL, P, I, I, P, P, P, SZ, I, I, I, I, I, F, F, U, U, P]),
     "medp_attn_fq_split_bwd": (I, [P, I, P, I, P, P, I, LL, P, P, I, LL, P, I, P, P, I, LL, P, SZ, I, I, I, I, I, F, F, U, U, P]),
@@ -150,8 +152,11 @@ SIGNATURES = {
     "medp_bce_mean": (I, [P, P, P, P, P, I, P]),
     "medp_adamw_chunk_elems": (I, []),
     "medp_adamw_multi": (I, [P, P, P, I, F, F, F, I, P, F, P]),
+    "medp_grad_sumsq_multi": (I, [P, P, P, I, P, F, P, P]),
+    "medp_adamw_multi_dscale": (I, [P, P, P, I, F, F, F, I, P, P, P]),
     "medp_traj_features": (I, [P, P, I, I, I, P]),
     "medp_gru_fwd": (I, [P, P, P, P, P, P, I, I, I, P]),
+    "medp_gru_fwd_f32": (I, [P, P, I, P, P, P, P, I, I, I, P]),
     "medp_gru_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
     "medp_rng_set_epoch_ptr": (I, [P]),
     "medp_counter_advance": (I, [P, P]),

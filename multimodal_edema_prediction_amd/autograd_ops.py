@@ -499,10 +499,11 @@ class AttnSmallFn(torch.autograd.Function):
     """Multi-head attention core.  q: [Lq, D] (shared by the batch) or [B, Lq, D]; kv: [B, Lk(+skip), 2D] fused K|V
     projection, of which rows `skip:` are attended (skip=1 drops the CLS row of the image tokens).  Returns
     ([B, Lq, D], attn_avg or None).  Head dim 64 with <= 32 queries over > 1024 keys: the split-key kernels, which also
-    return the rows' logsumexp that their backward consumes (saved with o)."""
+    return the rows' logsumexp that their backward consumes (saved with o).  `key_mask` (bool / uint8 [B, Lk], true = key ignored:
+    nn.MultiheadAttention's key_padding_mask) takes the masked wave-per-query kernels whatever the shape."""
 
     @staticmethod
-    def forward(ctx, q, kv, H, scale, p, seed, sid, skip, want_avg):
+    def forward(ctx, q, kv, H, scale, p, seed, sid, skip, want_avg, key_mask=None):
         q, kv = q.contiguous(), kv.contiguous()
         shared = q.dim() == 2
         B, Ltot, D2 = kv.shape
@@ -511,8 +512,14 @@ class AttnSmallFn(torch.autograd.Function):
         dh = D // H
         kview = kv[:, skip:, :D]
         vview = kv[:, skip:, D:]
-        split = _fq_split_route(kv, skip, Lq, Lk, dh)
-        if split:
+        split = key_mask is None and _fq_split_route(kv, skip, Lq, Lk, dh)
+        if key_mask is not None:
+            key_mask = key_mask.detach().to(torch.uint8).contiguous()
+            avg = torch.empty((B, Lq, Lk), dtype=F32, device=kv.device) if want_avg else None      # every element is written
+            o = Fn.attn_small_fwd(q, kview, vview, B, Lq, Lk, H, dh, scale, q_batch_stride=0 if shared else None,
+                                  kv_batch_stride=kv.stride(0), dropout_p=p, seed=seed, stream_id=sid, attn_avg=avg, key_mask=key_mask)
+            ctx.save_for_backward(q, kv)
+        elif split:
             o, lse, avg = Fn.attn_fq_split_fwd(q, kview, vview, B, Lq, Lk, H, scale, q_batch_stride=0 if shared else None,
                                                kv_batch_stride=kv.stride(0), dropout_p=p, seed=seed, stream_id=sid, want_avg=want_avg)
             ctx.save_for_backward(q, kv, o, lse)
@@ -522,6 +529,7 @@ class AttnSmallFn(torch.autograd.Function):
                                   kv_batch_stride=kv.stride(0), dropout_p=p, seed=seed, stream_id=sid, attn_avg=avg)
             ctx.save_for_backward(q, kv)
         ctx.cfg = (H, scale, p, seed, sid, skip, shared, split)
+        ctx.key_mask = key_mask
         if want_avg:
             ctx.mark_non_differentiable(avg)
         return o, avg
@@ -540,14 +548,15 @@ class AttnSmallFn(torch.autograd.Function):
             o, lse = ctx.saved_tensors[2:]
             dq, _, _ = Fn.attn_fq_split_bwd(do.contiguous(), o, lse, q, kv[:, skip:, :D], kv[:, skip:, D:], B, Lq, Lk, H, scale, **kw)
         else:
-            dq, _, _ = Fn.attn_small_bwd(do.contiguous(), q, kv[:, skip:, :D], kv[:, skip:, D:], B, Lq, Lk, H, D // H, scale, **kw)
+            dq, _, _ = Fn.attn_small_bwd(do.contiguous(), q, kv[:, skip:, :D], kv[:, skip:, D:], B, Lq, Lk, H, D // H, scale,
+                                         key_mask=ctx.key_mask, **kw)
         if shared:
             dq = Fn.colsum(dq.view(B, Lq * D)).view(Lq, D)
-        return dq, dkv, None, None, None, None, None, None, None
+        return dq, dkv, None, None, None, None, None, None, None, None
 
 
-def attn_small(q, kv, H, scale, p=0.0, seed=0, sid=0, skip=0, want_avg=False):
-    return AttnSmallFn.apply(q, kv, int(H), float(scale), float(p), int(seed), int(sid), int(skip), bool(want_avg))
+def attn_small(q, kv, H, scale, p=0.0, seed=0, sid=0, skip=0, want_avg=False, key_mask=None):
+    return AttnSmallFn.apply(q, kv, int(H), float(scale), float(p), int(seed), int(sid), int(skip), bool(want_avg), key_mask)
 
 
 # ---------------------------------------------------------------------------------------------- heads / logits

@@ -34,6 +34,8 @@ struct SmallAttnParams {
     float scale, drop_p, inv_keep;
     uint32_t seed, stream_id;
     const uint32_t* epoch;
+    const unsigned char* mask;   // [B, Lk] key-padding mask, non-zero = key ignored (the MASKED instantiations only)
+    long long mask_bs;
 };
 
 // <a, b> over dh floats: a in LDS (same address on every lane), b = this lane's own K / V row in global memory.  Rows are
@@ -68,17 +70,19 @@ __device__ __forceinline__ float weighted_col_sum(const float* __restrict__ w, c
     return acc;
 }
 
-// scores + softmax for one query row; returns p (post-softmax, pre-dropout) per owned key in pj[], writes nothing
-template <int NPER>
+// scores + softmax for one query row; returns p (post-softmax, pre-dropout) per owned key in pj[], writes nothing.
+// MASKED (nn.MultiheadAttention's key_padding_mask): a key whose byte in mrow[] is non-zero scores -inf and gets probability
+// exactly 0; a row with every key masked gets all-zero probabilities (no 0 * inf: the 1 / sum is guarded).
+template <int NPER, bool MASKED>
 __device__ __forceinline__ void row_softmax(const SmallAttnParams& p, const float* qrow, const float* kbase, int lane,
-                                            float (&pj)[NPER], bool vec) {
+                                            float (&pj)[NPER], bool vec, const unsigned char* mrow) {
     constexpr int nper = NPER;
     float mx = -INFINITY;
 #pragma unroll
     for (int i = 0; i < nper; ++i) {
         const int j = lane + 64 * i;
         float s = -INFINITY;
-        if (j < p.Lk) {
+        if (j < p.Lk && !(MASKED && mrow[j])) {
             s = dot_row(qrow, kbase + (size_t)j * p.ldk, p.dh, vec) * p.scale;
         }
         pj[i] = s;
@@ -88,18 +92,20 @@ __device__ __forceinline__ void row_softmax(const SmallAttnParams& p, const floa
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < nper; ++i) {
-        const float e = (lane + 64 * i < p.Lk) ? __expf(pj[i] - mx) : 0.f;
+        const bool live = MASKED ? pj[i] != -INFINITY : lane + 64 * i < p.Lk;
+        const float e = live ? __expf(pj[i] - mx) : 0.f;
         pj[i] = e;
         sum += e;
     }
-    const float inv = 1.0f / wave_sum(sum);
+    sum = wave_sum(sum);
+    const float inv = (MASKED && sum == 0.f) ? 0.f : 1.0f / sum;
 #pragma unroll
     for (int i = 0; i < nper; ++i) pj[i] *= inv;
 }
 
 constexpr int FWD_QCH = 8;     // queries per workgroup of the forward kernel (two per wave)
 
-template <int NPER>
+template <int NPER, bool MASKED>
 __global__ __launch_bounds__(256) void attn_small_fwd_kernel(const SmallAttnParams p, void* __restrict__ o, int ldo, int o_bf16,
                                                              float* __restrict__ attn_avg) {
     extern __shared__ float sm[];   // [4][Lk] probabilities, [4][dh] query row
@@ -113,6 +119,7 @@ __global__ __launch_bounds__(256) void attn_small_fwd_kernel(const SmallAttnPara
     const float* kbase = p.k + (size_t)b * p.kv_bs + h * p.dh;
     const float* vbase = p.v + (size_t)b * p.kv_bs + h * p.dh;
     const bool vec = (((p.dh | p.ldk | p.ldv) & 3) == 0) && ((((uintptr_t)kbase | (uintptr_t)vbase) & 15) == 0);
+    const unsigned char* mrow = MASKED ? p.mask + (size_t)b * p.mask_bs : nullptr;
     constexpr int nper = NPER;
     float pj[NPER];
     // a workgroup takes FWD_QCH queries (grid.y chunks): with all Lq queries in one workgroup a DuETT call (97 queries,
@@ -122,7 +129,7 @@ __global__ __launch_bounds__(256) void attn_small_fwd_kernel(const SmallAttnPara
         const float* qr = p.q + (size_t)b * p.q_bs + (size_t)qi * p.ldq + h * p.dh;
         if (lane < p.dh) sq[lane] = qr[lane];
         WAVE_LDS_SYNC();
-        row_softmax<NPER>(p, sq, kbase, lane, pj, vec);
+        row_softmax<NPER, MASKED>(p, sq, kbase, lane, pj, vec, mrow);
 #pragma unroll
         for (int i = 0; i < nper; ++i) {
             const int j = lane + 64 * i;
@@ -130,7 +137,9 @@ __global__ __launch_bounds__(256) void attn_small_fwd_kernel(const SmallAttnPara
                 float w = pj[i];
                 if (p.drop_p > 0.f) w *= dropout_scale(mixed_seed, p.stream_id, ((uint32_t)(b * p.H + h) * p.Lq + qi) * p.Lk + j, p.drop_p, p.inv_keep);
                 sp[j] = w;
-                if (attn_avg) atomicAdd(attn_avg + ((size_t)b * p.Lq + qi) * p.Lk + j, w / (float)p.H);
+                if constexpr (!MASKED) {      // the masked form averages the heads in attn_small_avg_kernel (one plain store per element)
+                    if (attn_avg) atomicAdd(attn_avg + ((size_t)b * p.Lq + qi) * p.Lk + j, w / (float)p.H);
+                }
             }
         }
         WAVE_LDS_SYNC();
@@ -143,11 +152,49 @@ __global__ __launch_bounds__(256) void attn_small_fwd_kernel(const SmallAttnPara
     }
 }
 
+// attn_avg[b][q][j] = (1/H) sum_h P_bhqj dropmask_bhqj for the MASKED form: a wave per (batch, query) recomputes the row of every
+// head in turn and adds them in head order, then stores each element once — bitwise reproducible, where the atomic adds of the
+// unmasked forward are not (the order of the heads' workgroups varies).  Masked keys get exactly 0.
+template <int NPER>
+__global__ __launch_bounds__(256) void attn_small_avg_kernel(const SmallAttnParams p, float* __restrict__ attn_avg) {
+    __shared__ float sQ[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x, qi = blockIdx.y * 4 + wave;
+    if (qi >= p.Lq) return;                      // whole waves leave; no block barrier below
+    const uint32_t mixed_seed = p.drop_p > 0.f ? medp_mix_epoch(p.seed, p.epoch) : 0u;
+    const unsigned char* mrow = p.mask + (size_t)b * p.mask_bs;
+    float pj[NPER], acc[NPER];
+#pragma unroll
+    for (int i = 0; i < NPER; ++i) acc[i] = 0.f;
+    for (int h = 0; h < p.H; ++h) {
+        const float* kbase = p.k + (size_t)b * p.kv_bs + h * p.dh;
+        const bool vec = (((p.dh | p.ldk) & 3) == 0) && (((uintptr_t)kbase & 15) == 0);
+        if (lane < p.dh) sQ[wave][lane] = p.q[(size_t)b * p.q_bs + (size_t)qi * p.ldq + h * p.dh + lane];
+        WAVE_LDS_SYNC();
+        row_softmax<NPER, true>(p, sQ[wave], kbase, lane, pj, vec, mrow);
+#pragma unroll
+        for (int i = 0; i < NPER; ++i) {
+            const int j = lane + 64 * i;
+            if (j < p.Lk) {
+                float w = pj[i];
+                if (p.drop_p > 0.f) w *= dropout_scale(mixed_seed, p.stream_id, ((uint32_t)(b * p.H + h) * p.Lq + qi) * p.Lk + j, p.drop_p, p.inv_keep);
+                acc[i] += w / (float)p.H;
+            }
+        }
+        WAVE_LDS_SYNC();
+    }
+#pragma unroll
+    for (int i = 0; i < NPER; ++i) {
+        const int j = lane + 64 * i;
+        if (j < p.Lk) attn_avg[((size_t)b * p.Lq + qi) * p.Lk + j] = acc[i];
+    }
+}
+
 // Backward.  Per chunk of QCH queries: phase 1 (wave per query) recomputes P, forms dS, writes both to LDS and dQ to
 // global; phase 2 (thread per (key, d)) adds the chunk's contribution to dK, dV of this (batch, head).
 constexpr int QCH = 8;
 
-template <int NPER>
+template <int NPER, bool MASKED>
 __global__ __launch_bounds__(256) void attn_small_bwd_kernel(const SmallAttnParams p, const float* __restrict__ dout, int lddo,
                                                              float* __restrict__ dq, int lddq, float* __restrict__ dk, int lddk,
                                                              float* __restrict__ dv, int lddv, long long dkv_bs) {
@@ -165,6 +212,7 @@ __global__ __launch_bounds__(256) void attn_small_bwd_kernel(const SmallAttnPara
     float* dkbase = dk + (size_t)b * dkv_bs + h * p.dh;
     float* dvbase = dv + (size_t)b * dkv_bs + h * p.dh;
     const bool vec = (((p.dh | p.ldk | p.ldv) & 3) == 0) && ((((uintptr_t)kbase | (uintptr_t)vbase) & 15) == 0);
+    const unsigned char* mrow = MASKED ? p.mask + (size_t)b * p.mask_bs : nullptr;
     constexpr int nper = NPER;
     float pj[NPER];
 
@@ -180,7 +228,7 @@ __global__ __launch_bounds__(256) void attn_small_bwd_kernel(const SmallAttnPara
             const int qi = c0 + ql;
             const float* qr = sQ + ql * p.dh;
             const float* dor = sDO + ql * p.dh;
-            row_softmax<NPER>(p, qr, kbase, lane, pj, vec);
+            row_softmax<NPER, MASKED>(p, qr, kbase, lane, pj, vec, mrow);
             // dP_j = <dO, V_j> * dropmask_j ; delta = sum_j P_j*dropmask_j*... (softmax bwd on the pre-dropout p)
             float dpj[NPER];
             float delta = 0.f;
@@ -452,6 +500,42 @@ int check(const SmallAttnParams& p) {
     return 0;
 }
 
+// the wave-per-query launches, shared by the plain and the key-masked exports
+template <bool MASKED>
+void launch_small_fwd(const SmallAttnParams& p, void* o, int ldo, int o_bf16, float* attn_avg, hipStream_t st) {
+    const size_t lds = (size_t)(4 * p.Lk + 4 * p.dh) * sizeof(float);
+    const int nper = (p.Lk + 63) / 64;
+    const dim3 grid(p.B * p.H, (p.Lq + FWD_QCH - 1) / FWD_QCH);
+    if (nper <= 1) attn_small_fwd_kernel<1, MASKED><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
+    else if (nper <= 2) attn_small_fwd_kernel<2, MASKED><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
+    else if (nper <= 4) attn_small_fwd_kernel<4, MASKED><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
+    else if (nper <= 8) attn_small_fwd_kernel<8, MASKED><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
+    else attn_small_fwd_kernel<MAXK_PER_LANE, MASKED><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
+}
+
+size_t small_bwd_lds(const SmallAttnParams& p) { return (size_t)(2 * QCH * p.Lk + 2 * QCH * p.dh) * sizeof(float); }
+
+template <bool MASKED>
+void launch_small_bwd(const SmallAttnParams& p, const float* dout, int lddo, float* dq, int lddq, float* dk, int lddk, float* dv,
+                      int lddv, long long dkv_bs, hipStream_t st) {
+    MEDP_ONCE_PER_DEVICE({
+        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<1, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<2, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<4, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<8, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<MAXK_PER_LANE, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    });
+    const size_t lds = small_bwd_lds(p);
+    const int nper = (p.Lk + 63) / 64, nb = p.B * p.H;
+#define MEDP_BWD_ARGS p, dout, lddo, dq, lddq, dk, lddk, dv, lddv, dkv_bs
+    if (nper <= 1) attn_small_bwd_kernel<1, MASKED><<<nb, 256, lds, st>>>(MEDP_BWD_ARGS);
+    else if (nper <= 2) attn_small_bwd_kernel<2, MASKED><<<nb, 256, lds, st>>>(MEDP_BWD_ARGS);
+    else if (nper <= 4) attn_small_bwd_kernel<4, MASKED><<<nb, 256, lds, st>>>(MEDP_BWD_ARGS);
+    else if (nper <= 8) attn_small_bwd_kernel<8, MASKED><<<nb, 256, lds, st>>>(MEDP_BWD_ARGS);
+    else attn_small_bwd_kernel<MAXK_PER_LANE, MASKED><<<nb, 256, lds, st>>>(MEDP_BWD_ARGS);
+#undef MEDP_BWD_ARGS
+}
+
 }  // namespace
 
 extern "C" int medp_attn_small_fwd(const float* q, int ldq, long long q_batch_stride, const float* k, const float* v, int ldkv,
@@ -476,14 +560,7 @@ extern "C" int medp_attn_small_fwd(const float* q, int ldq, long long q_batch_st
         MEDP_LAUNCH_CHECK("medp_attn_small_fwd(few queries)");
         return 0;
     }
-    const size_t lds = (size_t)(4 * Lk + 4 * dh) * sizeof(float);
-    const int nper = (Lk + 63) / 64;
-    const dim3 grid(B * H, (Lq + FWD_QCH - 1) / FWD_QCH);
-    if (nper <= 1) attn_small_fwd_kernel<1><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
-    else if (nper <= 2) attn_small_fwd_kernel<2><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
-    else if (nper <= 4) attn_small_fwd_kernel<4><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
-    else if (nper <= 8) attn_small_fwd_kernel<8><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
-    else attn_small_fwd_kernel<MAXK_PER_LANE><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
+    launch_small_fwd<false>(p, o, ldo, o_bf16, attn_avg, st);
     MEDP_LAUNCH_CHECK("medp_attn_small_fwd");
     return 0;
 }
@@ -513,24 +590,49 @@ extern "C" int medp_attn_small_bwd(const float* dout, int lddo, const float* q, 
         MEDP_LAUNCH_CHECK("medp_attn_small_bwd(few queries)");
         return 0;
     }
-    const size_t lds = (size_t)(2 * QCH * Lk + 2 * QCH * dh) * sizeof(float);
-    MEDP_CHECK_ARG(lds <= 160 * 1024, "attn_small_bwd: Lk too large for LDS");
-    MEDP_ONCE_PER_DEVICE({
-        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<MAXK_PER_LANE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    const int nper = (Lk + 63) / 64;
-    hipStream_t st = (hipStream_t)stream;
-#define MEDP_BWD_ARGS p, dout, lddo, dq, lddq, dk, lddk, dv, lddv, dkv_batch_stride
-    if (nper <= 1) attn_small_bwd_kernel<1><<<B * H, 256, lds, st>>>(MEDP_BWD_ARGS);
-    else if (nper <= 2) attn_small_bwd_kernel<2><<<B * H, 256, lds, st>>>(MEDP_BWD_ARGS);
-    else if (nper <= 4) attn_small_bwd_kernel<4><<<B * H, 256, lds, st>>>(MEDP_BWD_ARGS);
-    else if (nper <= 8) attn_small_bwd_kernel<8><<<B * H, 256, lds, st>>>(MEDP_BWD_ARGS);
-    else attn_small_bwd_kernel<MAXK_PER_LANE><<<B * H, 256, lds, st>>>(MEDP_BWD_ARGS);
-#undef MEDP_BWD_ARGS
+    MEDP_CHECK_ARG(small_bwd_lds(p) <= 160 * 1024, "attn_small_bwd: Lk too large for LDS");
+    launch_small_bwd<false>(p, dout, lddo, dq, lddq, dk, lddk, dv, lddv, dkv_batch_stride, (hipStream_t)stream);
     MEDP_LAUNCH_CHECK("medp_attn_small_bwd");
+    return 0;
+}
+
+// ---- key-masked form (nn.MultiheadAttention's key_padding_mask; the trajectory probe's 7 queries over V x W window tokens) -------
+// Always the wave-per-query kernels: neither the few-query kernels above nor the split-key route take a mask.
+extern "C" int medp_attn_small_masked_fwd(const float* q, int ldq, long long q_batch_stride, const float* k, const float* v, int ldkv,
+                                          long long kv_batch_stride, void* o, int ldo, int o_bf16, float* attn_avg, int B, int Lq,
+                                          int Lk, int H, int dh, float scale, float dropout_p, unsigned seed, unsigned stream_id,
+                                          void* stream, const unsigned char* key_mask, long long mask_batch_stride) {
+    SmallAttnParams p{q, k, v, ldq, ldkv, ldkv, q_batch_stride, kv_batch_stride, B, Lq, Lk, H, dh, scale, dropout_p, 1.0f / (1.0f - dropout_p), seed, stream_id, medp_rng_epoch_ptr(), key_mask, mask_batch_stride};
+    MEDP_TRY(check(p));
+    MEDP_CHECK_ARG(o && key_mask && mask_batch_stride >= Lk, "attn_small_masked_fwd: null output / mask, or mask rows shorter than Lk");
+    hipStream_t st = (hipStream_t)stream;
+    launch_small_fwd<true>(p, o, ldo, o_bf16, nullptr, st);
+    MEDP_LAUNCH_CHECK("medp_attn_small_masked_fwd");
+    if (attn_avg) {
+        const int nper = (Lk + 63) / 64;
+        const dim3 grid(B, (Lq + 3) / 4);
+        if (nper <= 1) attn_small_avg_kernel<1><<<grid, 256, 0, st>>>(p, attn_avg);
+        else if (nper <= 2) attn_small_avg_kernel<2><<<grid, 256, 0, st>>>(p, attn_avg);
+        else if (nper <= 4) attn_small_avg_kernel<4><<<grid, 256, 0, st>>>(p, attn_avg);
+        else if (nper <= 8) attn_small_avg_kernel<8><<<grid, 256, 0, st>>>(p, attn_avg);
+        else attn_small_avg_kernel<MAXK_PER_LANE><<<grid, 256, 0, st>>>(p, attn_avg);
+        MEDP_LAUNCH_CHECK("medp_attn_small_masked_fwd(attn_avg)");
+    }
+    return 0;
+}
+
+extern "C" int medp_attn_small_masked_bwd(const float* dout, int lddo, const float* q, int ldq, long long q_batch_stride, const float* k,
+                                          const float* v, int ldkv, long long kv_batch_stride, float* dq, int lddq, float* dk, int lddk,
+                                          float* dv, int lddkv_unused, long long dkv_batch_stride, int B, int Lq, int Lk, int H, int dh,
+                                          float scale, float dropout_p, unsigned seed, unsigned stream_id, void* stream,
+                                          const unsigned char* key_mask, long long mask_batch_stride) {
+    (void)lddkv_unused;
+    SmallAttnParams p{q, k, v, ldq, ldkv, ldkv, q_batch_stride, kv_batch_stride, B, Lq, Lk, H, dh, scale, dropout_p, 1.0f / (1.0f - dropout_p), seed, stream_id, medp_rng_epoch_ptr(), key_mask, mask_batch_stride};
+    MEDP_TRY(check(p));
+    MEDP_CHECK_ARG(dout && dq && dk && dv, "attn_small_masked_bwd: null gradient buffer");
+    MEDP_CHECK_ARG(key_mask && mask_batch_stride >= Lk, "attn_small_masked_bwd: null mask, or mask rows shorter than Lk");
+    MEDP_CHECK_ARG(small_bwd_lds(p) <= 160 * 1024, "attn_small_masked_bwd: Lk too large for LDS");
+    launch_small_bwd<true>(p, dout, lddo, dq, lddq, dk, lddk, dv, lddk, dkv_batch_stride, (hipStream_t)stream);
+    MEDP_LAUNCH_CHECK("medp_attn_small_masked_bwd");
     return 0;
 }

@@ -129,6 +129,47 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const GruFwd p) {
     }
 }
 
+// The fp32 kernel mode's forward (a parity instrument, not a fast path): a workgroup per sequence, a thread per hidden unit, h in
+// LDS (double buffered: one barrier per step), W_hh TRANSPOSED in fp32 so that the threads of a wave read consecutive columns,
+// libm exp / tanh.  Same outputs as gru_fwd_kernel (hseq, gates r | z | n, hn = W_hn h + b_hn), so the backward is shared.
+__global__ __launch_bounds__(D) void gru_fwd_f32_kernel(const float* __restrict__ gi, const float* __restrict__ wt, int ldw,
+                                                        const float* __restrict__ bhh, float* __restrict__ hseq,
+                                                        float* __restrict__ gates, float* __restrict__ hn, int T) {
+    __shared__ float hs[2][D];
+    const int u = threadIdx.x;
+    const float br = bhh[u], bz = bhh[D + u], bn = bhh[2 * D + u];
+    float h = 0.f;
+    hs[0][u] = 0.f;
+    __syncthreads();
+    for (int t = 0; t < T; ++t) {
+        const int cur = t & 1;
+        float ar = 0.f, az = 0.f, an = 0.f;
+        for (int k = 0; k < D; ++k) {
+            const float hk = hs[cur][k];
+            const float* w = wt + (size_t)k * ldw + u;
+            ar = fmaf(hk, w[0], ar);
+            az = fmaf(hk, w[D], az);
+            an = fmaf(hk, w[2 * D], an);
+        }
+        const size_t row = (size_t)blockIdx.x * T + t;
+        const float* g = gi + row * 3 * D;
+        const float r = 1.0f / (1.0f + expf(-(g[u] + ar + br)));
+        const float z = 1.0f / (1.0f + expf(-(g[D + u] + az + bz)));
+        const float ghn = an + bn;
+        const float n = tanhf(g[2 * D + u] + r * ghn);
+        h = (1.0f - z) * n + z * h;
+        hs[cur ^ 1][u] = h;
+        hseq[row * D + u] = h;
+        if (gates) {
+            gates[row * 3 * D + u] = r;
+            gates[row * 3 * D + D + u] = z;
+            gates[row * 3 * D + 2 * D + u] = n;
+            hn[row * D + u] = ghn;
+        }
+        __syncthreads();
+    }
+}
+
 struct GruBwd {
     const float* dh;            // [S, T, D]   gradient w.r.t. every hidden state that left the GRU
     const float* gates;         // [S, T, 3D]
@@ -229,6 +270,17 @@ extern "C" int medp_gru_fwd(const float* gi, const void* whh_bf16, const float* 
     const GruFwd p{gi, (const bf16_t*)whh_bf16, bhh, hseq, gates, hn, S, T};
     gru_fwd_kernel<<<(S + SB - 1) / SB, 256, 0, (hipStream_t)stream>>>(p);
     MEDP_LAUNCH_CHECK("medp_gru_fwd");
+    return 0;
+}
+
+extern "C" int medp_gru_fwd_f32(const float* gi, const float* whh_t, int ld_whh_t, const float* bhh, float* hseq, float* gates,
+                                float* hn, int S, int T, int d, void* stream) {
+    MEDP_CHECK_ARG(gi && whh_t && bhh && hseq, "gru_fwd_f32: null argument");
+    MEDP_CHECK_ARG((gates == nullptr) == (hn == nullptr), "gru_fwd_f32: gates and hn are saved together or not at all");
+    MEDP_CHECK_ARG(d == D, "gru_fwd_f32: hidden size %d is not built (the kernels are written for %d)", d, D);
+    MEDP_CHECK_ARG(S > 0 && T > 0 && ld_whh_t >= 3 * D, "gru_fwd_f32: bad shape S=%d T=%d ld=%d", S, T, ld_whh_t);
+    gru_fwd_f32_kernel<<<S, D, 0, (hipStream_t)stream>>>(gi, whh_t, ld_whh_t, bhh, hseq, gates, hn, T);
+    MEDP_LAUNCH_CHECK("medp_gru_fwd_f32");
     return 0;
 }
 

@@ -233,20 +233,30 @@ def attn_dh64_bwd(dout: torch.Tensor, qkv: torch.Tensor, o: torch.Tensor, lse: t
 
 
 def attn_small_fwd(q, k, v, B, Lq, Lk, H, dh, scale, *, q_batch_stride=None, kv_batch_stride=None, out_dtype=F32,
-                   dropout_p=0.0, seed=0, stream_id=0, attn_avg=None):
-    """q fp32 rows [.., H*dh] (ld = q.stride(-2)); k, v fp32 with a common row stride."""
+                   dropout_p=0.0, seed=0, stream_id=0, attn_avg=None, key_mask=None):
+    """q fp32 rows [.., H*dh] (ld = q.stride(-2)); k, v fp32 with a common row stride.  `key_mask`: uint8 [B, Lk], non-zero =
+    key ignored (the masked kernels; `attn_avg` then need not be zeroed)."""
     ldq, ldkv = q.stride(-2), k.stride(-2)
     assert v.stride(-2) == ldkv
     qbs = Lq * ldq if q_batch_stride is None else q_batch_stride
     kbs = Lk * ldkv if kv_batch_stride is None else kv_batch_stride
     o = torch.empty((B, Lq, H * dh), dtype=out_dtype, device=k.device)
-    check(lib().medp_attn_small_fwd(ptr(q), ldq, qbs, ptr(k), ptr(v), ldkv, kbs, ptr(o), H * dh, int(out_dtype == BF16),
-                                     ptr(attn_avg), B, Lq, Lk, H, dh, scale, dropout_p, seed, stream_id, stream()), "attn_small_fwd")
+    args = (ptr(q), ldq, qbs, ptr(k), ptr(v), ldkv, kbs, ptr(o), H * dh, int(out_dtype == BF16), ptr(attn_avg), B, Lq, Lk, H, dh,
+            scale, dropout_p, seed, stream_id, stream())
+    if key_mask is None:
+        check(lib().medp_attn_small_fwd(*args), "attn_small_fwd")
+    else:
+        check(lib().medp_attn_small_masked_fwd(*args, *_key_mask_args(key_mask, B, Lk)), "attn_small_masked_fwd")
     return o
 
 
+def _key_mask_args(key_mask, B, Lk):
+    assert key_mask.dtype == torch.uint8 and key_mask.shape == (B, Lk) and key_mask.stride(1) == 1
+    return ptr(key_mask), key_mask.stride(0)
+
+
 def attn_small_bwd(dout, q, k, v, B, Lq, Lk, H, dh, scale, *, q_batch_stride=None, kv_batch_stride=None, dropout_p=0.0,
-                   seed=0, stream_id=0, dkv_out=None):
+                   seed=0, stream_id=0, dkv_out=None, key_mask=None):
     """Returns (dq [B,Lq,D], dk, dv).  dk/dv are the two column halves of one [B, Lk, 2D] buffer (`dkv_out`, which may be a
     strided view, e.g. rows 1.. of a [B, Lk+1, 2D] tensor) so the fused K|V projection gets its gradient without a concat."""
     ldq, ldkv = q.stride(-2), k.stride(-2)
@@ -259,9 +269,12 @@ def attn_small_bwd(dout, q, k, v, B, Lq, Lk, H, dh, scale, *, q_batch_stride=Non
     assert dkv_out.stride(-1) == 1 and dkv_out.shape[-1] == 2 * D
     d2 = dout.reshape(B * Lq, D)
     base = dkv_out.data_ptr()
-    check(lib().medp_attn_small_bwd(ptr(d2), _ld(d2), ptr(q), ldq, qbs, ptr(k), ptr(v), ldkv, kbs, ptr(dq), D, base,
-                                     dkv_out.stride(-2), base + 4 * D, 0, dkv_out.stride(0), B, Lq, Lk, H, dh, scale, dropout_p,
-                                     seed, stream_id, stream()), "attn_small_bwd")
+    args = (ptr(d2), _ld(d2), ptr(q), ldq, qbs, ptr(k), ptr(v), ldkv, kbs, ptr(dq), D, base, dkv_out.stride(-2), base + 4 * D, 0,
+            dkv_out.stride(0), B, Lq, Lk, H, dh, scale, dropout_p, seed, stream_id, stream())
+    if key_mask is None:
+        check(lib().medp_attn_small_bwd(*args), "attn_small_bwd")
+    else:
+        check(lib().medp_attn_small_masked_bwd(*args, *_key_mask_args(key_mask, B, Lk)), "attn_small_masked_bwd")
     return dq, dkv_out[..., :D], dkv_out[..., D:]
 
 

@@ -741,3 +741,65 @@ class GraphedProbeStep:
         self.g.replay()
         self.opt.note_external_step()
         return self.out
+
+
+class GraphedTrajectoryProbeStep:
+    """The trajectory-probe step (trajectory_probe.train_probe_batch; analysis/train_trajectory_probe.py:205-215) as ONE captured
+    graph: encoder -> masked cross-attention -> head -> masked BCE -> backward -> global-norm clip -> AdamW.  The step is
+    latency-bound (312 k parameters, ~150 short launches), so the capture is most of what there is to gain.  The clip runs inside
+    the graph: the optimiser is a `FusedAdamW(max_grad_norm=...)`, whose norm, factor and update read device memory only.
+    `step(x_ts, y, mask)` copies a batch (host or device; x_ts stacked [B, T, 2V] or the collate's tuple) into the static buffers
+    and replays; the returned loss and `opt.last_grad_norm` are device tensors."""
+
+    def __del__(self):
+        ep = self.__dict__.get("epoch")
+        if ep is not None:
+            _release_epoch(ep)
+
+    def __init__(self, probe, loss_fn, optimizer, example_x, example_y, example_mask, device, warmup: int = 3, before_capture=None):
+        self.probe, self.loss_fn, self.opt, self.device = probe, loss_fn, optimizer, device
+        self.x = _stacked(example_x).to(device).float().clone()
+        self.y = example_y.to(device).float().clone()
+        self.mask = example_mask.to(device).float().clone()
+        self.epoch = torch.zeros(1, dtype=torch.int32, device=device)
+        _register_epoch(self.epoch)
+        snap = _TrainSnapshot([p for g in optimizer.param_groups for p in g["params"] if p.requires_grad], optimizer, [probe], self.epoch)
+        s = new_stream(device)
+        s.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(s):
+            for _ in range(max(int(warmup), 1)):
+                self._whole()
+        torch.cuda.current_stream(device).wait_stream(s)
+        torch.cuda.synchronize(device)
+        self.opt.zero_grad(set_to_none=True)
+        snap.restore()                                      # the warm-up steps trained: put the probe and its optimiser state back
+        torch.cuda.synchronize(device)
+        if before_capture is not None:
+            before_capture()
+        self.g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.g):
+            note_capture_origin(device)
+            self.out = self._whole()
+        torch.cuda.synchronize(device)
+        self.opt._step = int(self.opt.dev_step.item())      # capture ran opt.step() on the host without executing it
+
+    def _whole(self):
+        check(lib().medp_counter_advance(ptr(self.epoch), stream()), "counter_advance")
+        self.opt.zero_grad(set_to_none=True)
+        loss = self.loss_fn(self.probe(self.x), self.y, self.mask)
+        loss.backward()
+        self.opt.step()
+        return {"loss": loss.detach()}
+
+    def step(self, x_ts=None, y=None, mask=None) -> dict:
+        if x_ts is not None:
+            x_ts = _stacked(x_ts)
+            if x_ts.data_ptr() != self.x.data_ptr():
+                self.x.copy_(x_ts, non_blocking=True)
+        if y is not None:
+            self.y.copy_(y, non_blocking=True)
+            self.mask.copy_(mask, non_blocking=True)
+        self.opt.refresh_lrs()
+        self.g.replay()
+        self.opt.note_external_step()
+        return self.out

@@ -54,12 +54,25 @@ class FusedAdamW(torch.optim.Optimizer):
     through a RING of pinned staging buffers, each guarded by an event recorded behind its host->device copy (the host may
     run several steps ahead of the GPU — bench.py reads the loss of step k-1, a training loop may never sync).  A captured
     graph holds only the KERNEL node; the upload for replay k is enqueued on the stream right before the replay
-    (`refresh_lrs`), so replay k always sees the learning rates of step k."""
+    (`refresh_lrs`), so replay k always sees the learning rates of step k.
+
+    `max_grad_norm` (default None: launches exactly as without it) clips by the global gradient norm ON THE DEVICE, in effect
+    `torch.nn.utils.clip_grad_norm_(params, max_grad_norm)` followed by AdamW: a sum-of-squares pass over the same table, a
+    one-workgroup finish that leaves the norm in `last_grad_norm` (a device tensor; `step` never reads it on the host) and the
+    factor min(1, max_norm / (norm + 1e-6)) next to it, then the update with that factor applied to every gradient as it is read.
+    The pointers are fixed from the first step on, so a captured step replays the clip.  One difference from the torch pair: the
+    gradients are not rewritten, `p.grad` still holds the UNCLIPPED values after the step."""
 
     RING = 4
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None):
+        if max_grad_norm is not None and not max_grad_norm >= 0:
+            raise ValueError(f"FusedAdamW: max_grad_norm must be >= 0 or None, got {max_grad_norm!r}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._clip = None             # device [norm, scale], written by the norm kernels of every step
+        self._partials = None         # one sum of squares per workgroup of the block map
+        self.last_grad_norm = None    # view of _clip[0:1]
         self._step = 0
         self._chunk = lib().medp_adamw_chunk_elems()
         self._map_key = None
@@ -124,6 +137,7 @@ class FusedAdamW(torch.optim.Optimizer):
             self._ring = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
             self._ring_ev = [torch.cuda.Event() for _ in range(self.RING)]
             self._descs_dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self._partials = torch.empty(len(bt), dtype=torch.float32, device=dev) if self.max_grad_norm is not None else None
             self._map_key = key
         self._entries = entries
         for i, (p, st, lr, wd) in enumerate(entries):
@@ -134,13 +148,27 @@ class FusedAdamW(torch.optim.Optimizer):
             self._upload_table()
         if self.dev_step is None or self.dev_step.device != dev:
             self.dev_step = torch.full((1,), self._step - 1, dtype=torch.int32, device=dev)
-        check(lib().medp_counter_advance(ptr(self.dev_step), stream()), "counter_advance")
-        check(lib().medp_adamw_multi(ptr(self._descs_dev), ptr(self._blk_t), ptr(self._blk_c), self._blk_t.numel(), betas[0], betas[1],
-                                     eps, self._step, ptr(self.dev_step), 1.0, stream()), "adamw_multi")
+        if self.max_grad_norm is not None and (self._clip is None or self._clip.device != dev):
+            if capturing:
+                raise RuntimeError("FusedAdamW: the clip buffers must exist before a graph capture (run warm-up steps first)")
+            self._clip = torch.zeros(2, dtype=torch.float32, device=dev)
+            self.last_grad_norm = self._clip[0:1]
+        self._launch(betas, eps)
         # the kernel wrote the parameters behind torch's back: bump their version counters (host-side only, no launch) so
         # autograd's saved-tensor checks and the bf16 weight caches keyed on `_version` see the update
         torch.autograd.graph.increment_version([p for p, *_ in entries])
         return loss
+
+    def _launch(self, betas, eps) -> None:
+        """Step counter, (global-norm pass,) update: over the table as it stands on the device."""
+        table = (ptr(self._descs_dev), ptr(self._blk_t), ptr(self._blk_c), self._blk_t.numel())
+        check(lib().medp_counter_advance(ptr(self.dev_step), stream()), "counter_advance")
+        if self.max_grad_norm is None:
+            check(lib().medp_adamw_multi(*table, betas[0], betas[1], eps, self._step, ptr(self.dev_step), 1.0, stream()), "adamw_multi")
+            return
+        check(lib().medp_grad_sumsq_multi(*table, ptr(self._partials), self.max_grad_norm, ptr(self._clip), stream()), "grad_sumsq_multi")
+        check(lib().medp_adamw_multi_dscale(*table, betas[0], betas[1], eps, self._step, ptr(self.dev_step),
+                                            self._clip.data_ptr() + 4, stream()), "adamw_multi_dscale")
 
     # ---- graph-replay support: the table captured with the step (its gradient pointers) + this step's learning rates ------
     def refresh_lrs(self) -> None:
@@ -156,9 +184,7 @@ class FusedAdamW(torch.optim.Optimizer):
         update without rebuilding the table on the host and without a second graph."""
         betas, eps = self.param_groups[0]["betas"], self.param_groups[0]["eps"]
         self._step += 1
-        check(lib().medp_counter_advance(ptr(self.dev_step), stream()), "counter_advance")
-        check(lib().medp_adamw_multi(ptr(self._descs_dev), ptr(self._blk_t), ptr(self._blk_c), self._blk_t.numel(), betas[0], betas[1],
-                                     eps, self._step, ptr(self.dev_step), 1.0, stream()), "adamw_multi")
+        self._launch(betas, eps)
         torch.autograd.graph.increment_version([p for p, *_ in self._entries])
 
     def current_lrs(self) -> list:

@@ -6,6 +6,7 @@ out of scope; the cohort comes from cohort.py (the reference's own smoke-test re
 
     python -m multimodal_edema_prediction_amd.train_synthetic teacher --ckpt_dir runs/t0 --epochs 3
     python -m multimodal_edema_prediction_amd.train_synthetic student --teacher_ckpt runs/t0/best.pt --ckpt_dir runs/s0
+    python -m multimodal_edema_prediction_amd.train_synthetic trajectory_probe --ckpt_dir runs/p0      (or: --stage trajectory_probe ...)
     torchrun --nproc-per-node N -m multimodal_edema_prediction_amd.train_synthetic teacher ...      (one rank per GPU, RCCL)
 
 Defaults follow training_duett/run.py (lr 8e-5, weight decay 5e-2, warm-up 300 steps, backbone / query LR x0.2, patience 5,
@@ -89,6 +90,19 @@ def parse_args(argv=None) -> argparse.Namespace:
     s.add_argument("--kd_name", default="vanilla_kl")
     s.add_argument("--kd_T", type=float, default=4.0)
     s.add_argument("--kd_alpha", type=float, default=0.5)
+    p = sub.add_parser("trajectory_probe", help="time-series-only probe over LocalTrajectoryEncoder (analysis/train_trajectory_probe.py)")
+    for name, typ, default in (("--ckpt_dir", str, None), ("--epochs", int, 30), ("--patience", int, 5), ("--batch_size", int, 128),
+                               ("--lr", float, 3e-4), ("--weight_decay", float, 1e-2), ("--grad_clip", float, 1.0),
+                               ("--d_model", int, 128), ("--gru_layers", int, 1), ("--n_heads", int, 4), ("--dropout", float, 0.1),
+                               ("--trajectory_windows", str, "6,12,24"), ("--n_timesteps", int, 24), ("--n_vars", int, 48),
+                               ("--d_static", int, 8), ("--n_train", int, 4096), ("--n_val", int, 1024), ("--n_test", int, 1024),
+                               ("--num_workers", int, 0), ("--seed", int, 42), ("--limit_batches", int, 0)):
+        p.add_argument(name, type=typ, default=default, required=default is None)
+    p.add_argument("--eager", action="store_true", help="run train_probe_batch from Python instead of the captured-graph step")
+    p.add_argument("--learnable_labels", action="store_true", help="labels depend on the inputs (so that AUROC moves)")
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if len(argv) >= 2 and argv[0] == "--stage":          # `--stage NAME ...` is the sub-command spelled as an option
+        argv = argv[1:]
     args = ap.parse_args(argv)
     # graph mode is the default; the eager engine step stays for --eager and for what the captured step does not carry
     # (the aux residual KL of engine.py:149-165 is an engine extra, off by default)
@@ -328,9 +342,68 @@ def train_student(args) -> dict:
     return {"best_val_auroc": best, "test": test, "history": history, "ckpt": best_path}
 
 
+# ------------------------------------------------------------------------------------------------------------------ trajectory probe
+def train_trajectory_probe(args) -> dict:
+    """analysis/train_trajectory_probe.py:280-381 on the synthetic cohort without images (one GPU): AdamW with the global-norm
+    clip, cosine LR per EPOCH down to 1 % of lr, best.pt on validation macro-AUROC with the reference's keys, patience, test."""
+    from . import trajectory_probe as tp
+    device = _device(0)
+    os.makedirs(args.ckpt_dir, exist_ok=True)
+    torch.manual_seed(args.seed)
+    labels = tuple(PATHOLOGY_LABELS)
+    windows = tuple(int(w) for w in args.trajectory_windows.split(",") if w.strip())
+    if args.d_model % args.n_heads:
+        raise ValueError("d_model must be divisible by n_heads")
+    ccfg = CohortCfg(n_timesteps=args.n_timesteps, n_vars=args.n_vars, d_static=args.d_static, image_size=0, n_labels=len(labels),
+                     seed=args.seed, learnable=bool(args.learnable_labels))
+    train_ds, val_ds, test_ds = (SyntheticCohort(ccfg, n, "student", off) for n, off in
+                                 ((args.n_train, 0), (args.n_val, 10_000_000), (args.n_test, 20_000_000)))
+    ts_vars = [f"var_{i}" for i in range(args.n_vars)]
+    model = tp.TrajectoryPathologyProbe(n_vars=args.n_vars, n_pathologies=len(labels), n_timesteps=args.n_timesteps, d_model=args.d_model,
+                                        gru_layers=args.gru_layers, n_heads=args.n_heads, dropout=args.dropout,
+                                        recency_windows=windows).to(device)
+    opt = FusedAdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.grad_clip)
+    sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=max(args.epochs, 1), eta_min=args.lr * 0.01)
+    loaders = {k: make_loader(ds, args.batch_size, False, args.num_workers, "student", 0, 1) for k, ds in (("val", val_ds), ("test", test_ds))}
+    best_path, best, stale, history, gstep = os.path.join(args.ckpt_dir, "best.pt"), -float("inf"), 0, [], None
+    for epoch in range(1, args.epochs + 1):
+        model.train()
+        total, n = 0.0, 0
+        for step, raw in enumerate(make_loader(train_ds, args.batch_size, True, args.num_workers, "student", 0, 1, epoch_seed=args.seed + epoch)):
+            if args.limit_batches and step >= args.limit_batches:
+                break
+            b = tp.move_batch(raw, device)
+            if args.graph and gstep is None:
+                from .graph_step import GraphedTrajectoryProbeStep
+                gstep = GraphedTrajectoryProbeStep(model, tp.masked_bce, opt, b["x_ts"], b["y"], b["mask"], device)
+            out = gstep.step(b["x_ts"], b["y"], b["mask"]) if args.graph else tp.train_probe_batch(model, b, opt)
+            total, n = total + float(out["loss"]), n + 1
+        val = tp.evaluate(model, loaders["val"], device, labels)
+        sched.step()
+        _log(0, f"[probe ep{epoch:02d}] train_BCE {total / max(n, 1):.5f}  val_BCE {val['loss']:.5f}  val macro-AUROC {val['macro_auroc']:.4f}  "
+                f"macro-AUPRC {val['macro_auprc']:.4f}  lr {opt.param_groups[0]['lr']:.2e}")
+        history.append({"epoch": epoch, "train_loss": total / max(n, 1), "val_macro_auroc": val["macro_auroc"]})
+        if val["macro_auroc"] > best + 1e-6:
+            best, stale = val["macro_auroc"], 0
+            torch.save({"model": model.state_dict(), "epoch": epoch, "val": val, "args": vars(args), "labels": labels, "ts_vars": ts_vars},
+                       best_path)
+        else:
+            stale += 1
+            if args.patience > 0 and stale >= args.patience:
+                _log(0, f"[probe] early stop at epoch {epoch}; best val macro-AUROC {best:.4f}")
+                break
+    state = {"epoch": None}
+    if os.path.exists(best_path):          # a validation AUROC that is never defined (one class only) saves nothing
+        state = torch.load(best_path, map_location=device, weights_only=False)
+        model.load_state_dict(state["model"])
+    test = tp.evaluate(model, loaders["test"], device, labels)
+    _log(0, f"[probe] test macro-AUROC {test['macro_auroc']:.4f} macro-AUPRC {test['macro_auprc']:.4f} (best epoch {state['epoch']})")
+    return {"best_val_auroc": best, "test": test, "history": history, "ckpt": best_path}
+
+
 def main(argv=None) -> dict:
     args = parse_args(argv)
-    out = train_teacher(args) if args.stage == "teacher" else train_student(args)
+    out = {"teacher": train_teacher, "student": train_student, "trajectory_probe": train_trajectory_probe}[args.stage](args)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
     return out

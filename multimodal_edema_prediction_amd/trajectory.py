@@ -30,6 +30,14 @@ def traj_features(x: torch.Tensor, n_vars: int) -> torch.Tensor:
     return out
 
 
+def _gru_weight_t_bf16(w_hh: torch.Tensor) -> torch.Tensor:
+    """W_hh^T as the backward kernel reads it: bf16 whatever the precision mode (it is bf16 MFMA only; the fp32 mode's cached
+    operand is fp32 and would be read as garbage)."""
+    if Fn.precision() != "fp32":
+        return A.weight_t_bf16(w_hh)
+    return Fn.transpose_to_bf16(w_hh.detach().contiguous())
+
+
 class GruFn(torch.autograd.Function):
     """gi [S,T,3d] fp32 (x_t W_ih^T + b_ih), W_hh [3d,d], b_hh [3d] -> every hidden state [S,T,d]; h0 = 0."""
 
@@ -42,8 +50,13 @@ class GruFn(torch.autograd.Function):
         hseq = torch.empty((S, T, d), dtype=F32, device=gi.device)
         gates = torch.empty((S, T, d3), dtype=F32, device=gi.device) if need else None
         hn = torch.empty((S, T, d), dtype=F32, device=gi.device) if need else None
-        check(lib().medp_gru_fwd(ptr(gi), ptr(A.weight_bf16(w_hh)), ptr(b_hh.detach().contiguous()), ptr(hseq), ptr(gates), ptr(hn),
-                                 S, T, d, stream()), "gru_fwd")
+        if Fn.precision() == "fp32":                 # fp32 weights and products; the backward below stays the bf16 kernel
+            wt = A.weight_t_bf16(w_hh)               # (fp32 mode: the fp32 [d, 3d] transpose)
+            check(lib().medp_gru_fwd_f32(ptr(gi), ptr(wt), wt.stride(0), ptr(b_hh.detach().contiguous()), ptr(hseq), ptr(gates), ptr(hn),
+                                         S, T, d, stream()), "gru_fwd_f32")
+        else:
+            check(lib().medp_gru_fwd(ptr(gi), ptr(A.weight_bf16(w_hh)), ptr(b_hh.detach().contiguous()), ptr(hseq), ptr(gates), ptr(hn),
+                                     S, T, d, stream()), "gru_fwd")
         ctx.save_for_backward(gates, hn, hseq, w_hh)
         return hseq
 
@@ -55,7 +68,7 @@ class GruFn(torch.autograd.Function):
         dgi = torch.empty((S, T, 3 * d), dtype=F32, device=dh.device)
         dghn = torch.empty((S, T, d), dtype=F32, device=dh.device)
         dgh16 = torch.empty((S, T, 3 * d), dtype=BF16, device=dh.device)
-        check(lib().medp_gru_bwd(ptr(dh), ptr(gates), ptr(hn), ptr(hseq), ptr(A.weight_t_bf16(w_hh)), ptr(dgi), ptr(dghn), ptr(dgh16),
+        check(lib().medp_gru_bwd(ptr(dh), ptr(gates), ptr(hn), ptr(hseq), ptr(_gru_weight_t_bf16(w_hh)), ptr(dgi), ptr(dghn), ptr(dgh16),
                                  S, T, d, stream()), "gru_bwd")
         # dW_hh = sum over (sequence, step) of dgh^T h_{t-1}: the transposed GEMM over the stored rows; h_{-1} = 0
         hprev = torch.zeros_like(hseq)
