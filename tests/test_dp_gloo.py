@@ -97,7 +97,7 @@ def test_two_rank_gradient_allreduce_matches_full_batch():
 
 
 def _arena_worker(rank, world, port, q):
-    """The graph step's N > 1 exchange (dp.FlatGradArena, used by graph_step._GraphedStep): used-parameter discovery, grads as
+    """The graph step's N > 1 exchange (dp.FlatGradArena, used by graph_step._PipelinedStep): used-parameter discovery, grads as
     arena views, bucketed async mean all-reduce, AdamW with weight decay that must NOT touch the never-used parameters."""
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     dp.init_distributed("gloo")

@@ -360,3 +360,26 @@ def test_graphed_probe_step_equals_the_eager_probe_step():
     for (k, a), (_, b2) in zip(me.named_parameters(), mg.named_parameters()):
         if a.requires_grad:
             assert float((a - b2).abs().max()) <= 1e-6, k
+
+
+def test_graphed_probe_step_refuses_frozen_weights_changed_after_capture():
+    """As test_gpu_pipeline.test_replay_refuses_frozen_weights_changed_after_capture, for the probe step: its graph reads the frozen
+    encoder's PREPARED weights by address too.  Writing a frozen parameter and calling the probe eagerly rebuilds them; the step
+    keeps the captured ones alive and raises instead of training on stale weights."""
+    from multimodal_edema_prediction_amd.cohort import CohortCfg, make_batch
+    from multimodal_edema_prediction_amd.graph_step import GraphedProbeStep
+    from multimodal_edema_prediction_amd.linear_probe import RadDinoClassifier, masked_bce_with_logits_loss
+    from multimodal_edema_prediction_amd.optim import FusedAdamW
+    dev = torch.device("cuda")
+    b = make_batch(CohortCfg(n_timesteps=8, n_vars=4, d_static=8, image_size=112, n_labels=7, seed=5), 0, 4, mode="teacher")
+    torch.manual_seed(0)
+    m = RadDinoClassifier("synthetic", num_classes=7, dropout=0.0).to(dev)
+    m.train()
+    opt = FusedAdamW([p for p in m.parameters() if p.requires_grad], lr=1e-3, weight_decay=1e-4)
+    gs = GraphedProbeStep(m, masked_bce_with_logits_loss, opt, b["pixel_values"], b["y_multi"], b["y_multi_mask"], dev, warmup=1)
+    assert np.isfinite(float(gs.step(b["pixel_values"], b["y_multi"].float(), b["y_multi_mask"].float())["loss"]))
+    with torch.no_grad():
+        m.encoder.backbone.layernorm.weight.mul_(1.5)       # a frozen parameter changes ...
+        m(b["pixel_values"].to(dev))                        # ... and an eager call rebuilds the prepared weights
+    with pytest.raises(RuntimeError, match="frozen weights were modified"):
+        gs.step(b["pixel_values"], b["y_multi"].float(), b["y_multi_mask"].float())

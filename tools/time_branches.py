@@ -77,7 +77,7 @@ with torch.cuda.stream(side):
         gs._train_fwd_bwd()
         opt.step()
     with torch.cuda.graph(g_vit, stream=side):
-        gs._frozen_forward(0)
+        gs._frozen_forward()
 torch.cuda.synchronize()
 t_train = replay_ms(g_train.replay)
 t_vit = replay_ms(g_vit.replay)
