@@ -468,7 +468,13 @@ int medp_add_bcast(const float* a, const float* b, float* out, long long per_bat
  *   dgh_bf16 [S,T,3d] (r | z | n parts of the gradient w.r.t. h W_hh^T + b_hh; dW_hh = dgh^T h_prev is a medp_gemm_bf16_tn).
  *   whh_t_bf16 [d,3d] = W_hh transposed.
  * medp_gru_fwd_f32: the forward with fp32 weights, fp32 products and libm exp / tanh (the fp32 kernel mode: a parity instrument);
- *   whh_t [d, ld_whh_t >= 3d] fp32 = W_hh transposed; same outputs, so medp_gru_bwd serves it too. */
+ *   whh_t [d, ld_whh_t >= 3d] fp32 = W_hh transposed; same outputs, so medp_gru_bwd serves it too.
+ * Stacked GRU (n_layers > 1; layer k >= 1 reads every hidden state of layer k - 1, with dropout between the layers in training):
+ * medp_gru_fwd_h16: medp_gru_fwd that also writes hseq_bf16 [S,T,d] = bf16(h_t * mask), the next layer's input, from the registers
+ *   that hold h_t; mask = the inter-layer dropout keep-mask times 1 / (1 - p), drawn by (seed, stream_id, RNG epoch) on the flat
+ *   element index of [S,T,d]; dropout_p = 0: a plain rounding.
+ * medp_gru_bwd_dgi16: medp_gru_bwd that also writes dgi_bf16 [S,T,3d], the bf16 copy of dgi an upper layer's dW_ih = dgi^T x and
+ *   dx = dgi W_ih GEMMs read. */
 int medp_traj_features(const float* x, float* out, int B, int T, int V, void* stream);
 int medp_gru_fwd(const float* gi, const void* whh_bf16, const float* bhh, float* hseq, float* gates, float* hn, int S, int T, int d,
                  void* stream);
@@ -476,6 +482,10 @@ int medp_gru_fwd_f32(const float* gi, const float* whh_t, int ld_whh_t, const fl
                      int T, int d, void* stream);
 int medp_gru_bwd(const float* dh, const float* gates, const float* hn, const float* hseq, const void* whh_t_bf16, float* dgi,
                  float* dghn, void* dgh_bf16, int S, int T, int d, void* stream);
+int medp_gru_fwd_h16(const float* gi, const void* whh_bf16, const float* bhh, float* hseq, float* gates, float* hn, void* hseq_bf16,
+                     float dropout_p, unsigned seed, unsigned stream_id, int S, int T, int d, void* stream);
+int medp_gru_bwd_dgi16(const float* dh, const float* gates, const float* hn, const float* hseq, const void* whh_t_bf16, float* dgi,
+                       float* dghn, void* dgh_bf16, void* dgi_bf16, int S, int T, int d, void* stream);
 
 #ifdef __cplusplus
 }

@@ -158,6 +158,8 @@ SIGNATURES = {
     "medp_gru_fwd": (I, [P, P, P, P, P, P, I, I, I, P]),
     "medp_gru_fwd_f32": (I, [P, P, I, P, P, P, P, I, I, I, P]),
     "medp_gru_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
+    "medp_gru_fwd_h16": (I, [P, P, P, P, P, P, P, F, U, U, I, I, I, P]),
+    "medp_gru_bwd_dgi16": (I, [P, P, P, P, P, P, P, P, P, I, I, I, P]),
     "medp_rng_set_epoch_ptr": (I, [P]),
     "medp_counter_advance": (I, [P, P]),
 }

@@ -11,6 +11,11 @@
 // Backward walks the steps in reverse with the same ownership: the gate gradients of a step go through LDS as a 16 x 384 bf16
 // tile and dh_{t-1} += dgh W_hh uses the TRANSPOSED weight fragments (again register resident).  dW_hh and db_hh are a
 // transposed GEMM / column sums over the stored gate gradients afterwards (host side of the autograd node).
+//
+// Stacked GRU (n_layers > 1).  A layer hands its hidden states to the next one as a bf16 [S, T, 128] tensor written from the
+// registers that hold h_t (`hseq16`), already multiplied by the inter-layer dropout mask (flat element index of [S, T, 128]); the
+// upper layer's x_t W_ih^T is the same bf16 MFMA GEMM as layer 0's, and its backward reads a bf16 copy of dgi that gru_bwd_kernel
+// writes beside dgh16: no dropout pass and no cast pass between the layers.
 #include "common.h"
 
 namespace {
@@ -53,14 +58,31 @@ struct GruFwd {
     float* gates;               // [S, T, 3D]  r | z | n   (saved for backward; may be null)
     float* hn;                  // [S, T, D]   W_hn h + b_hn (saved for backward; may be null)
     int S, T;
+    // hand-over to the next layer of a stack (H16 kernels only): bf16(h_t * dropout mask), the flat index of [S, T, D] draws the mask
+    bf16_t* hseq16;             // [S, T, D] bf16
+    float drop_p, inv_keep;
+    uint32_t seed, sid;
+    const uint32_t* epoch;
 };
 
+// four consecutive hidden units of one (sequence, step) row -> hseq16, times the inter-layer dropout mask when p > 0
+__device__ __forceinline__ void store_h16(const GruFwd& p, uint32_t seed, size_t row, int u, f32x4 h) {
+    if (p.drop_p > 0.f) {
+        const uint32_t i0 = (uint32_t)(row * D + u);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) h[c] *= dropout_scale(seed, p.sid, i0 + c, p.drop_p, p.inv_keep);
+    }
+    *(uint2*)(p.hseq16 + row * D + u) = make_uint2(pack_bf2(h[0], h[1]), pack_bf2(h[2], h[3]));
+}
+
+template <bool H16>
 __global__ __launch_bounds__(256) void gru_fwd_kernel(const GruFwd p) {
     __shared__ __attribute__((aligned(16))) char hbuf[2][SB * HROW];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int fr = lane & 15, kq = lane >> 4;
     const int seq = blockIdx.x * SB + fr;
     const bool ok = seq < p.S;
+    const uint32_t seed = H16 ? medp_mix_epoch(p.seed, p.epoch) : 0u;
     // W_hh fragments: a-operand rows = gate columns g*128 + 32w + jb*16 + fr, k = hidden index
     bf16x8 wf[3][2][4];
     f32x4 bh[3][2];
@@ -123,6 +145,7 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const GruFwd p) {
                     *(f32x4*)(p.gates + row * 3 * D + 2 * D + u) = n;
                     *(f32x4*)(p.hn + row * D + u) = ghn;
                 }
+                if (H16) store_h16(p, seed, row, u, hnew);
             }
         }
         __syncthreads();
@@ -180,8 +203,10 @@ struct GruBwd {
     float* dghn;                // [S, T, D]   gradient w.r.t. W_hn h + b_hn
     bf16_t* dgh16;              // [S, T, 3D]  bf16 copy of dgh (operand of the dW_hh GEMM)
     int S, T;
+    bf16_t* dgi16;              // [S, T, 3D]  bf16 copy of dgi (DGI16 kernel only: operand of an upper layer's dW_ih and dx GEMMs)
 };
 
+template <bool DGI16>
 __global__ __launch_bounds__(256) void gru_bwd_kernel(const GruBwd p) {
     __shared__ __attribute__((aligned(16))) char gbuf[2][SB * GROW];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -235,6 +260,11 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const GruBwd p) {
                 *(uint2*)(p.dgh16 + row * 3 * D + u) = pr;
                 *(uint2*)(p.dgh16 + row * 3 * D + D + u) = pz;
                 *(uint2*)(p.dgh16 + row * 3 * D + 2 * D + u) = pn;
+                if (DGI16) {
+                    *(uint2*)(p.dgi16 + row * 3 * D + u) = pr;
+                    *(uint2*)(p.dgi16 + row * 3 * D + D + u) = pz;
+                    *(uint2*)(p.dgi16 + row * 3 * D + 2 * D + u) = make_uint2(pack_bf2(dnp[0], dnp[1]), pack_bf2(dnp[2], dnp[3]));
+                }
             }
         }
         __syncthreads();
@@ -267,9 +297,23 @@ extern "C" int medp_gru_fwd(const float* gi, const void* whh_bf16, const float* 
     MEDP_CHECK_ARG((gates == nullptr) == (hn == nullptr), "gru_fwd: gates and hn are saved together or not at all");
     MEDP_CHECK_ARG(d == D, "gru_fwd: hidden size %d is not built (the register plan is written for %d)", d, D);
     MEDP_CHECK_ARG(S > 0 && T > 0, "gru_fwd: bad shape S=%d T=%d", S, T);
-    const GruFwd p{gi, (const bf16_t*)whh_bf16, bhh, hseq, gates, hn, S, T};
-    gru_fwd_kernel<<<(S + SB - 1) / SB, 256, 0, (hipStream_t)stream>>>(p);
+    const GruFwd p{gi, (const bf16_t*)whh_bf16, bhh, hseq, gates, hn, S, T, nullptr, 0.f, 1.f, 0u, 0u, nullptr};
+    gru_fwd_kernel<false><<<(S + SB - 1) / SB, 256, 0, (hipStream_t)stream>>>(p);
     MEDP_LAUNCH_CHECK("medp_gru_fwd");
+    return 0;
+}
+
+extern "C" int medp_gru_fwd_h16(const float* gi, const void* whh_bf16, const float* bhh, float* hseq, float* gates, float* hn,
+                                void* hseq_bf16, float dropout_p, unsigned seed, unsigned stream_id, int S, int T, int d, void* stream) {
+    MEDP_CHECK_ARG(gi && whh_bf16 && bhh && hseq && hseq_bf16, "gru_fwd_h16: null argument");
+    MEDP_CHECK_ARG((gates == nullptr) == (hn == nullptr), "gru_fwd_h16: gates and hn are saved together or not at all");
+    MEDP_CHECK_ARG(d == D, "gru_fwd_h16: hidden size %d is not built (the register plan is written for %d)", d, D);
+    MEDP_CHECK_ARG(S > 0 && T > 0, "gru_fwd_h16: bad shape S=%d T=%d", S, T);
+    MEDP_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "gru_fwd_h16: dropout_p %g is not in [0, 1)", (double)dropout_p);
+    const GruFwd p{gi, (const bf16_t*)whh_bf16, bhh, hseq, gates, hn, S, T, (bf16_t*)hseq_bf16, dropout_p, 1.f / (1.f - dropout_p),
+                   seed, stream_id, medp_rng_epoch_ptr()};
+    gru_fwd_kernel<true><<<(S + SB - 1) / SB, 256, 0, (hipStream_t)stream>>>(p);
+    MEDP_LAUNCH_CHECK("medp_gru_fwd_h16");
     return 0;
 }
 
@@ -289,8 +333,19 @@ extern "C" int medp_gru_bwd(const float* dh, const float* gates, const float* hn
     MEDP_CHECK_ARG(dh && gates && hn && hseq && whh_t_bf16 && dgi && dghn && dgh_bf16, "gru_bwd: null argument");
     MEDP_CHECK_ARG(d == D, "gru_bwd: hidden size %d is not built (the register plan is written for %d)", d, D);
     MEDP_CHECK_ARG(S > 0 && T > 0, "gru_bwd: bad shape S=%d T=%d", S, T);
-    const GruBwd p{dh, gates, hn, hseq, (const bf16_t*)whh_t_bf16, dgi, dghn, (bf16_t*)dgh_bf16, S, T};
-    gru_bwd_kernel<<<(S + SB - 1) / SB, 256, 0, (hipStream_t)stream>>>(p);
+    const GruBwd p{dh, gates, hn, hseq, (const bf16_t*)whh_t_bf16, dgi, dghn, (bf16_t*)dgh_bf16, S, T, nullptr};
+    gru_bwd_kernel<false><<<(S + SB - 1) / SB, 256, 0, (hipStream_t)stream>>>(p);
     MEDP_LAUNCH_CHECK("medp_gru_bwd");
+    return 0;
+}
+
+extern "C" int medp_gru_bwd_dgi16(const float* dh, const float* gates, const float* hn, const float* hseq, const void* whh_t_bf16,
+                                  float* dgi, float* dghn, void* dgh_bf16, void* dgi_bf16, int S, int T, int d, void* stream) {
+    MEDP_CHECK_ARG(dh && gates && hn && hseq && whh_t_bf16 && dgi && dghn && dgh_bf16 && dgi_bf16, "gru_bwd_dgi16: null argument");
+    MEDP_CHECK_ARG(d == D, "gru_bwd_dgi16: hidden size %d is not built (the register plan is written for %d)", d, D);
+    MEDP_CHECK_ARG(S > 0 && T > 0, "gru_bwd_dgi16: bad shape S=%d T=%d", S, T);
+    const GruBwd p{dh, gates, hn, hseq, (const bf16_t*)whh_t_bf16, dgi, dghn, (bf16_t*)dgh_bf16, S, T, (bf16_t*)dgi_bf16};
+    gru_bwd_kernel<true><<<(S + SB - 1) / SB, 256, 0, (hipStream_t)stream>>>(p);
+    MEDP_LAUNCH_CHECK("medp_gru_bwd_dgi16");
     return 0;
 }

@@ -401,6 +401,19 @@ def train_trajectory_probe(args) -> dict:
     return {"best_val_auroc": best, "test": test, "history": history, "ckpt": best_path}
 
 
+def build_trajectory_probe_from_ckpt(state: dict):
+    """The probe a `trajectory_probe` best.pt was trained as: every constructor argument from the checkpoint's own args (`gru_layers`
+    among them, so a stacked encoder comes back stacked), weights loaded with strict=True; eval(), on the CPU until moved."""
+    from . import trajectory_probe as tp
+    a = state["args"]
+    windows = tuple(int(w) for w in a["trajectory_windows"].split(",") if w.strip())
+    model = tp.TrajectoryPathologyProbe(n_vars=a["n_vars"], n_pathologies=len(state["labels"]), n_timesteps=a["n_timesteps"],
+                                        d_model=a["d_model"], gru_layers=a.get("gru_layers", 1), n_heads=a["n_heads"],
+                                        dropout=a["dropout"], recency_windows=windows)
+    model.load_state_dict(state["model"], strict=True)
+    return model.eval()
+
+
 def main(argv=None) -> dict:
     args = parse_args(argv)
     out = {"teacher": train_teacher, "student": train_student, "trajectory_probe": train_trajectory_probe}[args.stage](args)
