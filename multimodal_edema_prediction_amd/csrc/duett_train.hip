@@ -267,9 +267,11 @@ __global__ __launch_bounds__(256) void embed_inputs_bwd_kernel(const float* __re
 }
 
 // ---- psi assembly (model :53-66) and its backward -------------------------------------------------------------------------
-// psi[b][t][v][:] = var_out[v][b*T+t][:] | tab_out[b][:] (v == V) | special[0] (masked timestep / masked event) | special[1] (t == T)
+// psi[b][t][v][:] = var_out[v][b*T+t][:] | tab_out[b][:] (v == V) | special[0] (masked timestep / masked event) | special[1] (t == T, event not masked at t = 0)
 __device__ __forceinline__ int psi_cell_kind(const float* __restrict__ xs, int b, int t, int v, int T, int V) {
-    if (t == T) return 3;                                   // REP row
+    // REP row; the reference extends the event mask to it with TIMESTEP 0's row (duett.py:250), so a variable whose event is masked
+    // there carries the MASKED embedding in the REP row too (every SSL batch: the masked event's count is -1 at all timesteps)
+    if (t == T) return (v < V && xs[(size_t)b * T * (2 * V + 1) + V + v] == -1.0f) ? 2 : 3;
     const float* row = xs + ((size_t)b * T + t) * (2 * V + 1);
     if (row[2 * V] == 1.0f) return 2;                       // masked timestep
     if (v == V) return 1;                                   // static column
@@ -383,7 +385,18 @@ __global__ __launch_bounds__(256) void add_bcast_kernel(const float* __restrict_
     }
 }
 
-int dw_chunks(int R) { return max(1, min(64, R / 96)); }
+// Chunk plan of the weight-gradient partial sums: R / 96 chunks (at most 64) while a chunk's dy and x rows fit the LDS budget, which
+// keeps the chunk boundaries (and so the bits of dW, db) of every shape that always fitted; wider layers (the grouped pathology heads,
+// K = 256, N = 64, at a batch of 121 rows or more) take as many chunks as the budget asks for instead of being refused.
+constexpr size_t GLINEAR_DW_LDS_BYTES = 150 * 1024;
+int dw_chunks(int R, int K, int N) {
+    if (R <= 0 || K <= 0 || N <= 0) return 0;
+    const int nc = max(1, min(64, R / 96));
+    const size_t max_rows = GLINEAR_DW_LDS_BYTES / 4 / ((size_t)N + K);
+    if (max_rows == 0) return 0;                               // not even one row fits: the launcher refuses
+    if ((size_t)((R + nc - 1) / nc) <= max_rows) return nc;
+    return (int)(((size_t)R + max_rows - 1) / max_rows);
+}
 
 }  // namespace
 
@@ -396,7 +409,9 @@ extern "C" int medp_glinear_fwd(const float* x, const float* W, const float* b, 
     MEDP_LAUNCH_CHECK("medp_glinear_fwd");
     return 0;
 }
-extern "C" size_t medp_glinear_bwd_workspace_bytes(int G, int R, int K, int N) { return (size_t)G * dw_chunks(R) * ((size_t)N * K + N) * 4; }
+extern "C" size_t medp_glinear_bwd_workspace_bytes(int G, int R, int K, int N) {
+    return G > 0 ? (size_t)G * dw_chunks(R, K, N) * ((size_t)N * K + N) * 4 : 0;
+}
 extern "C" int medp_glinear_bwd(const float* dy, const float* x, const float* W, float* dx, float* dW, float* db, float* workspace, int G,
                                 int R, int K, int N, void* stream) {
     MEDP_CHECK_ARG(dy && x && W && G > 0 && R > 0 && K > 0 && N > 0 && (size_t)N * K <= GLINEAR_MAX_FLOATS, "glinear_bwd: bad argument");
@@ -410,12 +425,14 @@ extern "C" int medp_glinear_bwd(const float* dy, const float* x, const float* W,
     }
     if (dW) {
         MEDP_CHECK_ARG(workspace && db, "glinear_bwd: dW needs db and a workspace");
-        const int nc = dw_chunks(R), rpc = (R + nc - 1) / nc;
+        const int nc = dw_chunks(R, K, N);
+        MEDP_CHECK_ARG(nc > 0, "glinear_bwd: one row of dy and x (N + K floats) must fit LDS");
+        const int rpc = (R + nc - 1) / nc;
         float* pw = workspace;
         float* pb = workspace + (size_t)G * nc * N * K;
-        MEDP_CHECK_ARG((size_t)rpc * (N + K) * 4 <= 150 * 1024, "glinear_bwd: rows-per-chunk x (N + K) floats must fit LDS");
+        MEDP_CHECK_ARG((size_t)rpc * (N + K) * 4 <= GLINEAR_DW_LDS_BYTES, "glinear_bwd: rows-per-chunk x (N + K) floats must fit LDS");
         MEDP_ONCE_PER_DEVICE({
-            (void)hipFuncSetAttribute((const void*)glinear_bwd_dw_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+            (void)hipFuncSetAttribute((const void*)glinear_bwd_dw_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GLINEAR_DW_LDS_BYTES);
         });
         glinear_bwd_dw_partial_kernel<<<dim3(nc, G), 256, (size_t)rpc * (N + K) * 4, s>>>(dy, x, pw, pb, R, K, N, rpc);
         MEDP_LAUNCH_CHECK("medp_glinear_bwd(partial)");
