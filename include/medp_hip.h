@@ -487,6 +487,35 @@ int medp_gru_fwd_h16(const float* gi, const void* whh_bf16, const float* bhh, fl
 int medp_gru_bwd_dgi16(const float* dh, const float* gates, const float* hn, const float* hseq, const void* whh_t_bf16, float* dgi,
                        float* dghn, void* dgh_bf16, void* dgi_bf16, int S, int T, int d, void* stream);
 
+/* ---- Raw-trajectory conditional probe (analysis/raw_trajectory_conditional_probe.py, default path) -------------------------
+ * All arithmetic is fp64, as in the reference.
+ * medp_raw_traj_summary: x [B,T,2V] fp32 (values | counts, the layout medp_traj_features reads) -> out [B,V,14] fp64 =
+ *   {last, mean, std, min, max | delta, slope24, slope_recent, recent_shift | observed_fraction, log_total_count,
+ *   time_since_last, recent_observed_fraction, log_recent_count}: _summarize_one_variable (:329-405) with one row per hour
+ *   (slot_idx = t), its NaN rules and its centred two-pass std / slopes.  1 <= recent_hours <= T, otherwise rc < 0.
+ * medp_offset_logistic_valgrad: objective and gradient of _fit_offset_weights (:578-584) for G candidate columns at once:
+ *   X [n, ldx >= F] row-major, y [n] (0 / 1 as fp64), offset [n], W [F,G], l2 [G] ->
+ *   obj [G] = mean(logaddexp(0, s) - y s) + 0.5 l2 w.w,  grad [F,G] = X^T (expit(s) - y) / n + l2 w,  s = offset + X w.
+ *   X is read from HBM once (a workgroup keeps its row block in LDS between the two halves; a row longer than the LDS budget,
+ *   F > 18432, is re-read through L2 instead).  Partial sums go through ws (medp_offset_logistic_ws_bytes) and are added in
+ *   a fixed order: bit-stable, no floating-point atomics.  1 <= G <= MEDP_OFFSET_LOGISTIC_MAX_G, F >= 1, n >= 1, otherwise rc < 0.
+ * medp_resampled_binary_metrics: out [R,3] = {BCE, AUROC, AUPRC} of R resampled replicates, one workgroup each.
+ *   y [N] u8; p [Rp,N] with Rp = 1 (one vector shared by all replicates) or Rp = R; replicate r gathers positions
+ *   idx[offsets[r] .. offsets[r+1]) (int32 in [0, N); offsets int64 [R+1]); idx = null: every replicate is the identity over
+ *   all N (offsets unused).  Probabilities are clipped to [1e-7, 1 - 1e-7] after the gather (_safe_metrics :109-119), sorted in
+ *   LDS; AUROC and AUPRC take one threshold per DISTINCT score (sklearn's roc_auc_score / average_precision_score on ties).
+ *   One class only: AUROC = AUPRC = NaN, BCE finite.  An empty replicate, or one with an index outside [0, N): NaN, NaN, NaN.
+ *   max_len = the longest replicate (the caller drew the indices); above MEDP_RESAMPLED_METRICS_MAX_LEN: rc < 0, no launch. */
+#define MEDP_OFFSET_LOGISTIC_MAX_G 8
+#define MEDP_RESAMPLED_METRICS_MAX_LEN 16384 /* 8-byte keys: 128 KiB of the CU's 160 KiB LDS, a power of two for the bitonic sort */
+int medp_raw_traj_summary(const float* x, double* out, int B, int T, int V, int recent_hours, void* stream);
+size_t medp_offset_logistic_ws_bytes(int n, int F, int G);
+int medp_offset_logistic_valgrad(const double* X, long long ldx, const double* y, const double* offset, const double* W,
+                                 const double* l2, double* obj, double* grad, void* ws, size_t ws_bytes, int n, int F, int G,
+                                 void* stream);
+int medp_resampled_binary_metrics(const unsigned char* y, const double* p, const int* idx, const long long* offsets, double* out,
+                                  int N, int Rp, int R, int max_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,10 @@ SIGNATURES = {
     "medp_gru_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
     "medp_gru_fwd_h16": (I, [P, P, P, P, P, P, P, F, U, U, I, I, I, P]),
     "medp_gru_bwd_dgi16": (I, [P, P, P, P, P, P, P, P, P, I, I, I, P]),
+    "medp_raw_traj_summary": (I, [P, P, I, I, I, I, P]),
+    "medp_offset_logistic_ws_bytes": (SZ, [I, I, I]),
+    "medp_offset_logistic_valgrad": (I, [P, LL, P, P, P, P, P, P, P, SZ, I, I, I, P]),
+    "medp_resampled_binary_metrics": (I, [P, P, P, P, P, I, I, I, I, P]),
     "medp_rng_set_epoch_ptr": (I, [P]),
     "medp_counter_advance": (I, [P, P]),
 }
