@@ -516,6 +516,46 @@ int medp_offset_logistic_valgrad(const double* X, long long ldx, const double* y
 int medp_resampled_binary_metrics(const unsigned char* y, const double* p, const int* idx, const long long* offsets, double* out,
                                   int N, int Rp, int R, int max_len, void* stream);
 
+/* ---- Conditional-information probe (analysis/conditional_information_probe.py; csrc/cond_probe.hip) -----------------------
+ * The device half of a batched damped-Newton fit of Pipeline(StandardScaler, LogisticRegression(C)) with a free, unpenalised
+ * intercept.  All arithmetic is fp64; no floating-point atomics; every reduction runs in a fixed order (two launches are
+ * bit-identical).  One launch serves P problems, described by a table of MedpProbeProblem: problem p reads the F columns
+ * X[r, col_off .. col_off + F) of one fp32 matrix X [N, ldx] for the rows r = rows[row_off .. row_off + n_rows) (int32 indices,
+ * ragged: the label's mask) and the labels y[r, y_col] of y fp32 [N, ldy].  The table is passed twice: table_host is checked
+ * before anything is launched, table_dev (the same bytes in device memory) is what the kernels read.  rows_total = the length of
+ * `rows`; the stretches of the problems follow one another in table order without overlap (per-row values live at a row's
+ * position in the list).  A row index outside [0, N) is never dereferenced; it turns the outputs of its problem into NaN.
+ * Layouts: theta, g [P, Fmax+1] (standardised space; entries [F, Fmax) are padding, the intercept is LAST, at index Fmax);
+ * mean, scale [P, Fmax] (padding: 0 and 1); H [P, Fmax+1, Fmax+1].
+ * medp_probe_moments: per problem and column the mean (fp64 sum of the widened values / n), the population variance (two-pass,
+ *   centred) and scale = sqrt(var), except that a constant column (var <= n eps var + (n mean eps)^2, StandardScaler's test) keeps 1.
+ * medp_logistic_newton_terms: with a_i = ((x_i - mean) / scale, 1), s_i = a_i.theta, p_i = expit(s_i), d_i = p_i (1 - p_i):
+ *   f [P] = mean_i BCE(s_i, y_i) + 0.5 l2 sum_{j<F} theta_j^2,  g = mean_i (p_i - y_i) a_i + l2 (theta_0 .. theta_{F-1}, 0) and, when
+ *   H is not null, H = mean_i d_i a_i a_i^T + l2 diag(1, .., 1, 0), written exactly symmetric; padded entries of g and H are 0,
+ *   with 1 on H's padded diagonal (a padded solve is well posed).  l2 [P] (the caller passes 1 / (C n)).  H = null: the
+ *   value-and-gradient mode of a line search.  ws: medp_probe_terms_ws_bytes(P, Fmax, longest problem, rows_total) bytes.
+ * medp_probe_scores: out[row_off + i] = sum_{j0 <= j < j1} theta_j (x_ij - mean_j) / scale_j (+ theta[Fmax] when add_intercept)
+ *   for the rows of ANY row list (another split, with the training moments); a column range gives one part of a score.
+ * All three: rc < 0, nothing launched, for a null pointer, P < 1, F < 1 or F > Fmax, fewer than 2 rows in a problem, columns
+ *   outside a row of X, rows outside the list, a label column outside y (terms), a column range outside [0, F] (scores). */
+typedef struct {
+    long long col_off; /* first column: element offset into a row of X */
+    long long row_off; /* its rows: rows[row_off .. row_off + n_rows) */
+    int n_rows, F, y_col;
+    int j0, j1;        /* medp_probe_scores only: the columns summed */
+    int reserved_;
+} MedpProbeProblem;
+int medp_probe_moments(const float* X, long long ldx, int N, const MedpProbeProblem* table_host, const MedpProbeProblem* table_dev,
+                       const int* rows, long long rows_total, double* mean, double* scale, int P, int Fmax, void* stream);
+size_t medp_probe_terms_ws_bytes(int P, int Fmax, int max_rows, long long rows_total);
+int medp_logistic_newton_terms(const float* X, long long ldx, int N, const float* y, int ldy, const MedpProbeProblem* table_host,
+                               const MedpProbeProblem* table_dev, const int* rows, long long rows_total, const double* theta,
+                               const double* mean, const double* scale, const double* l2, double* f, double* g, double* H, void* ws,
+                               size_t ws_bytes, int P, int Fmax, void* stream);
+int medp_probe_scores(const float* X, long long ldx, int N, const MedpProbeProblem* table_host, const MedpProbeProblem* table_dev,
+                      const int* rows, long long rows_total, const double* theta, const double* mean, const double* scale, double* out,
+                      int P, int Fmax, int add_intercept, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,11 @@ class MedpOperandJob(ctypes.Structure):
                 ("reserved_", I)]
 
 
+class MedpProbeProblem(ctypes.Structure):
+    """One problem of the conditional-information probe's table (include/medp_hip.h)."""
+    _fields_ = [("col_off", LL), ("row_off", LL), ("n_rows", I), ("F", I), ("y_col", I), ("j0", I), ("j1", I), ("reserved_", I)]
+
+
 # name -> (restype, argtypes); must list every function declared in include/medp_hip.h (tests/test_abi.py checks)
 SIGNATURES = {
     "medp_last_error": (c_char_p, []),
@@ -164,6 +169,10 @@ SIGNATURES = {
     "medp_offset_logistic_ws_bytes": (SZ, [I, I, I]),
     "medp_offset_logistic_valgrad": (I, [P, LL, P, P, P, P, P, P, P, SZ, I, I, I, P]),
     "medp_resampled_binary_metrics": (I, [P, P, P, P, P, I, I, I, I, P]),
+    "medp_probe_moments": (I, [P, LL, I, P, P, P, LL, P, P, I, I, P]),
+    "medp_probe_terms_ws_bytes": (SZ, [I, I, I, LL]),
+    "medp_logistic_newton_terms": (I, [P, LL, I, P, I, P, P, P, LL, P, P, P, P, P, P, P, P, SZ, I, I, P]),
+    "medp_probe_scores": (I, [P, LL, I, P, P, P, LL, P, P, P, P, I, I, I, P]),
     "medp_rng_set_epoch_ptr": (I, [P]),
     "medp_counter_advance": (I, [P, P]),
 }
