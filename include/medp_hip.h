@@ -556,6 +556,57 @@ int medp_probe_scores(const float* X, long long ldx, int N, const MedpProbeProbl
                       const int* rows, long long rows_total, const double* theta, const double* mean, const double* scale, double* out,
                       int P, int Fmax, int add_intercept, void* stream);
 
+/* ---- Linear-head probes (analysis/unimodal_linear_probe.py, analysis/logit_fusion_probe.py; csrc/head_probe.hip) ------------
+ * Minibatch AdamW on a tiny head over frozen features: every sequential step of ONE epoch in one launch.  fp32 in storage, as the
+ * reference; sums (logits, gradients, the loss, the valid count) are accumulated in fp64 and rounded once.  No floating-point
+ * atomics, every reduction in a fixed order: two launches on the same inputs are bit-identical.  functional.precision() is not
+ * consulted.
+ * medp_head_train_epoch: P independent problems, one workgroup each (a step depends on the one before it; there is no barrier
+ *   between workgroups).  Problem p trains z = (x o dropout) W^T + b on the rows perm[s bs .. (s+1) bs) of X for s = 0 .. S-1:
+ *     label_width = 0: every label reads the F columns X[r, col0 .. col0 + F); W [L, F]                    (Dropout -> Linear)
+ *     label_width = w > 0: label l reads the columns col0 + [l w, (l+1) w), F = L w; W [L, w]              (LogitFusionHead per_label, w = 2)
+ *   loss = sum(BCE(z, Y) M) / vc with vc = sum of M over ALL labels of the minibatch; vc = 0: zero gradients, AdamW still steps.
+ *   AdamW as torch.optim.AdamW on W and b, weight decay on both; t[0] (device) is the number of steps taken so far and is advanced
+ *   by S.  Dropout: element r_in_batch * F + j of step number k = t + 1 (1-based) is kept iff the counter hash of
+ *   (seed + k * 0x9E3779B9, stream_id, index) says so (medp_mix_epoch with the problem's own step count; the registered RNG epoch is
+ *   not read).  loss_out [2] = {sum over steps of loss * vc, sum of vc}.
+ *   A permutation entry outside [0, N) is never dereferenced: W, b and loss_out of its problem become NaN.
+ *   W and both moments live in LDS for the epoch when medp_head_train_onchip(F, L, label_width, bs) = 1, in (L2-resident) global
+ *   memory otherwise.  The table is passed twice: table_host is checked before anything is launched, table_dev (the same bytes in
+ *   device memory) is what the kernel reads.  rc < 0, nothing launched: a null pointer, P < 1, F outside [1, MEDP_HEAD_MAX_F],
+ *   L outside [1, MEDP_HEAD_MAX_L], bs outside [1, MEDP_HEAD_MAX_BS], S < 1 or S bs > N, label_width < 0 or L label_width != F,
+ *   ldx < col0 + F, ldy < L, dropout_p outside [0, 1).
+ * medp_head_scores: logits [n, L] fp32 of the rows `rows` [n] (int32 in [0, N); null: rows 0 .. n-1) under (W, b), label_width
+ *   honoured, and probs [L, n] fp64 = the fp32 value 1 / (1 + exp(-logit)) widened: the layout medp_resampled_binary_metrics reads.
+ *   A row outside [0, N) is not dereferenced: NaN. */
+#define MEDP_HEAD_MAX_F 32768
+#define MEDP_HEAD_MAX_L 16
+#define MEDP_HEAD_MAX_BS 1024
+typedef struct {
+    const float* X;         /* [N, ldx] features, read in place */
+    const float* Y;         /* [N, ldy] labels */
+    const float* M;         /* [N, ldy] 1 = known */
+    float* W;               /* [L, F] (label_width 0) or [L, label_width] */
+    float* b;               /* [L] */
+    float* mW;              /* Adam first / second moments, the shapes of W and b */
+    float* vW;
+    float* mb;
+    float* vb;
+    int* t;                 /* [1] steps taken so far */
+    const int* perm;        /* [S * bs] this epoch's row order */
+    double* loss_out;       /* [2] */
+    long long ldx;
+    int N, ldy, col0, F, L, label_width, bs, S;
+    double lr, weight_decay, beta1, beta2, eps;
+    float dropout_p;
+    unsigned seed, stream_id;
+    int reserved_;
+} MedpHeadProblem;
+int medp_head_train_onchip(int F, int L, int label_width, int bs);
+int medp_head_train_epoch(const MedpHeadProblem* table_host, const MedpHeadProblem* table_dev, int P, void* stream);
+int medp_head_scores(const float* X, long long ldx, int N, int col0, int F, int L, int label_width, const float* W, const float* b,
+                     const int* rows, int n, float* logits, double* probs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_longlong, c_size_t, c_uint, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_uint, c_void_p
 
 import torch
 
@@ -58,6 +58,14 @@ class MedpOperandJob(ctypes.Structure):
 class MedpProbeProblem(ctypes.Structure):
     """One problem of the conditional-information probe's table (include/medp_hip.h)."""
     _fields_ = [("col_off", LL), ("row_off", LL), ("n_rows", I), ("F", I), ("y_col", I), ("j0", I), ("j1", I), ("reserved_", I)]
+
+
+class MedpHeadProblem(ctypes.Structure):
+    """One problem of the linear-head trainer's table (include/medp_hip.h)."""
+    _fields_ = ([(n, P) for n in ("X", "Y", "M", "W", "b", "mW", "vW", "mb", "vb", "t", "perm", "loss_out")] + [("ldx", LL)]
+                + [(n, I) for n in ("N", "ldy", "col0", "F", "L", "label_width", "bs", "S")]
+                + [(n, c_double) for n in ("lr", "weight_decay", "beta1", "beta2", "eps")]
+                + [("dropout_p", F), ("seed", U), ("stream_id", U), ("reserved_", I)])
 
 
 # name -> (restype, argtypes); must list every function declared in include/medp_hip.h (tests/test_abi.py checks)
@@ -173,6 +181,9 @@ SIGNATURES = {
     "medp_probe_terms_ws_bytes": (SZ, [I, I, I, LL]),
     "medp_logistic_newton_terms": (I, [P, LL, I, P, I, P, P, P, LL, P, P, P, P, P, P, P, P, SZ, I, I, P]),
     "medp_probe_scores": (I, [P, LL, I, P, P, P, LL, P, P, P, P, I, I, I, P]),
+    "medp_head_train_onchip": (I, [I, I, I, I]),
+    "medp_head_train_epoch": (I, [P, P, I, P]),
+    "medp_head_scores": (I, [P, LL, I, I, I, I, I, P, P, P, I, P, P, P]),
     "medp_rng_set_epoch_ptr": (I, [P]),
     "medp_counter_advance": (I, [P, P]),
 }

@@ -1,0 +1,340 @@
+// Linear-head probes (reference analysis/unimodal_linear_probe.py `train_linear_head`, analysis/logit_fusion_probe.py
+// `train_fusion_head`; DESIGN.md "Linear-head probes"): minibatch AdamW on a tiny head over frozen features.
+//
+//   head_train_epoch_kernel  ALL sequential steps of one epoch of one problem per workgroup (grid = P problems).  A step:
+//       A  logits     wave per minibatch row, lanes stride the columns, one fp64 accumulator per label, a fixed butterfly;
+//       -  vc, g      vc = sum of M over the whole minibatch (a fixed-order block sum), g = (sigmoid(z) - y) M / vc into LDS,
+//                     the loss sum beside it;
+//       B  update     thread per column: dW[:, j] = sum over the rows IN ORDER of g[r, :] x[r, j] in fp64, then torch's AdamW on
+//                     W[:, j] and its moments; thread l < L does the same for b[l].
+//     The dropout factor of element (r, j) is regenerated from the counter hash in A and in B.  W and the two moments live in LDS
+//     for the whole epoch when they fit (head_onchip), in global memory (a few hundred KB: L2-resident) otherwise; b and its
+//     moments (<= 16 values) stay in global memory.  No workgroup waits for another.
+//   head_scores_kernel       logits and fp32 sigmoid probabilities of a row list, the summation order of phase A.
+// fp32 in storage; fp64 accumulators; no floating-point atomics; every reduction in a fixed order.
+#include "common.h"
+#include "medp_hip.h"
+
+namespace {
+
+constexpr float kNaNf = __builtin_nanf("");
+constexpr int HT_THREADS = 512, HT_WAVES = HT_THREADS / 64;
+constexpr int HS_THREADS = 256, HS_WAVES = HS_THREADS / 64, HS_ROWS = 32;   // scores: rows per workgroup
+constexpr int HEAD_LDS_BUDGET = 144 * 1024;                                  // of the CU's 160 KiB
+
+// labels padded to a compile-time count (the accumulators stay in registers)
+__host__ __device__ inline int head_lp(int L) { return L <= 2 ? 2 : L <= 8 ? 8 : 16; }
+__host__ __device__ inline long long head_nw(int F, int L, int w) { return w == 0 ? (long long)L * F : (long long)F; }
+__host__ __device__ inline long long head_g_bytes(int L, int bs) { return (long long)bs * head_lp(L) * 4; }
+__host__ __device__ inline bool head_onchip(int F, int L, int w, int bs) {
+    return head_g_bytes(L, bs) + 12 * head_nw(F, L, w) <= HEAD_LDS_BUDGET;
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// every thread gets the sum; waves are added in wave order
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+    v = wave_sum_f64(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < HT_WAVES; ++w) s += red[w];
+    return s;
+}
+
+struct AdamScalars {
+    float decay, omb1, beta2, omb2, step_size, bc2_sqrt, eps;
+};
+// torch.optim.AdamW, single-tensor path: mul_(1 - lr wd); lerp_(g, 1 - b1); mul_(b2).addcmul_(g, g, 1 - b2);
+// denom = sqrt(v) / sqrt(1 - b2^t) + eps; addcdiv_(m, denom, -lr / (1 - b1^t))
+__device__ __forceinline__ void adamw(float* p, float* m, float* v, float g, const AdamScalars& a) {
+    const float pn = *p * a.decay;
+    const float mn = *m + a.omb1 * (g - *m);
+    const float vn = *v * a.beta2 + (a.omb2 * g) * g;
+    const float denom = sqrtf(vn) / a.bc2_sqrt + a.eps;
+    *p = pn + (-a.step_size * mn) / denom;
+    *m = mn;
+    *v = vn;
+}
+
+// dot products of one row with every label's weights: lanes stride the columns, the result (all lanes) per label in acc[]
+template <int LP>
+__device__ __forceinline__ void row_dots(const float* __restrict__ xr, const float* Wp, int F, int L, int lane, bool drop, uint32_t seed,
+                                         uint32_t sid, uint32_t idx0, float p, float inv_keep, double (&acc)[LP]) {
+#pragma unroll
+    for (int l = 0; l < LP; ++l) acc[l] = 0.0;
+#pragma unroll 2
+    for (int j = lane; j < F; j += 64) {
+        float xv = xr[j];
+        if (drop) xv *= dropout_scale(seed, sid, idx0 + (uint32_t)j, p, inv_keep);
+#pragma unroll
+        for (int l = 0; l < LP; ++l)
+            if (l < L) acc[l] = fma((double)xv, (double)Wp[(size_t)l * F + j], acc[l]);
+    }
+#pragma unroll
+    for (int l = 0; l < LP; ++l) acc[l] = wave_sum_f64(acc[l]);
+}
+
+template <int LP, bool ONCHIP>
+__device__ __forceinline__ void head_epoch(const MedpHeadProblem& pb, float* gs, float* st, double* red) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int F = pb.F, L = pb.L, w = pb.label_width, bs = pb.bs;
+    const int nW = (int)head_nw(F, L, w);
+    float* Wp = ONCHIP ? st : pb.W;
+    float* mW = ONCHIP ? st + nW : pb.mW;
+    float* vW = ONCHIP ? st + 2 * nW : pb.vW;
+    if (ONCHIP)
+        for (int e = tid; e < nW; e += HT_THREADS) {
+            Wp[e] = pb.W[e];
+            mW[e] = pb.mW[e];
+            vW[e] = pb.vW[e];
+        }
+    for (int e = tid; e < bs * LP; e += HT_THREADS) gs[e] = 0.f;          // the label padding stays zero
+    __syncthreads();
+    const float* Xc = pb.X + pb.col0;
+    const float p = pb.dropout_p, inv_keep = 1.f / (1.f - p);
+    const bool drop = p > 0.f;
+    const int t0 = pb.t[0];
+    double b1t = pow(pb.beta1, (double)t0), b2t = pow(pb.beta2, (double)t0);
+    AdamScalars a;
+    a.decay = (float)(1.0 - pb.lr * pb.weight_decay);
+    a.omb1 = (float)(1.0 - pb.beta1);
+    a.beta2 = (float)pb.beta2;
+    a.omb2 = (float)(1.0 - pb.beta2);
+    a.eps = (float)pb.eps;
+    double run_l = 0.0, run_v = 0.0;
+    for (int s = 0; s < pb.S; ++s) {
+        const int t = t0 + s + 1;
+        const uint32_t seed = pb.seed + (uint32_t)t * 0x9E3779B9u;          // medp_mix_epoch with the problem's own step count
+        const int* pr = pb.perm + (size_t)s * bs;
+        b1t *= pb.beta1;
+        b2t *= pb.beta2;
+        a.step_size = (float)(pb.lr / (1.0 - b1t));
+        a.bc2_sqrt = (float)sqrt(1.0 - b2t);
+        // ---- A: logits into gs
+        if (w == 0) {
+            for (int r = wave; r < bs; r += HT_WAVES) {
+                double acc[LP];
+                row_dots<LP>(Xc + (size_t)pr[r] * pb.ldx, Wp, F, L, lane, drop, seed, pb.stream_id, (uint32_t)r * (uint32_t)F, p, inv_keep, acc);
+                double z = 0.0;
+#pragma unroll
+                for (int l = 0; l < LP; ++l)
+                    if (lane == l) z = acc[l];
+                if (lane < L) gs[r * LP + lane] = (float)(z + (double)pb.b[lane]);
+            }
+        } else {
+            for (int e = tid; e < bs * L; e += HT_THREADS) {
+                const int r = e / L, l = e % L;
+                const float* xr = Xc + (size_t)pr[r] * pb.ldx;
+                double acc = 0.0;
+                for (int k = 0; k < w; ++k) {
+                    const int j = l * w + k;
+                    float xv = xr[j];
+                    if (drop) xv *= dropout_scale(seed, pb.stream_id, (uint32_t)r * (uint32_t)F + (uint32_t)j, p, inv_keep);
+                    acc = fma((double)xv, (double)Wp[j], acc);
+                }
+                gs[r * LP + l] = (float)(acc + (double)pb.b[l]);
+            }
+        }
+        // ---- vc over the whole minibatch, then g = (sigmoid(z) - y) M / vc and the loss sum
+        double part = 0.0;
+        for (int e = tid; e < bs * L; e += HT_THREADS) part += (double)pb.M[(size_t)pr[e / L] * pb.ldy + e % L];
+        const double vc = block_sum_f64(part, red);                          // its barriers also publish the logits
+        part = 0.0;
+        for (int e = tid; e < bs * L; e += HT_THREADS) {
+            const int r = e / L, l = e % L;
+            const size_t o = (size_t)pr[r] * pb.ldy + l;
+            const double z = (double)gs[r * LP + l], y = (double)pb.Y[o], m = (double)pb.M[o];
+            const double ex = exp(-fabs(z));
+            part += (fmax(z, 0.0) - y * z + log1p(ex)) * m;
+            const double sg = z >= 0.0 ? 1.0 / (1.0 + ex) : ex / (1.0 + ex);
+            gs[r * LP + l] = vc > 0.0 ? (float)((sg - y) * m / vc) : 0.f;   // vc = 0: the reference's loss is logits.sum() * 0
+        }
+        const double lsum = block_sum_f64(part, red);                        // publishes g
+        if (vc > 0.0) {
+            run_l += lsum / vc * vc;
+            run_v += vc;
+        }
+        // ---- B: gradient of every column in row order, AdamW
+        for (int j = tid; j < F; j += HT_THREADS) {
+            if (w == 0) {
+                double acc[LP];
+#pragma unroll
+                for (int l = 0; l < LP; ++l) acc[l] = 0.0;
+#pragma unroll 4
+                for (int r = 0; r < bs; ++r) {
+                    float xv = Xc[(size_t)pr[r] * pb.ldx + j];
+                    if (drop) xv *= dropout_scale(seed, pb.stream_id, (uint32_t)r * (uint32_t)F + (uint32_t)j, p, inv_keep);
+#pragma unroll
+                    for (int l = 0; l < LP; ++l) acc[l] = fma((double)gs[r * LP + l], (double)xv, acc[l]);
+                }
+#pragma unroll
+                for (int l = 0; l < LP; ++l)
+                    if (l < L) adamw(Wp + (size_t)l * F + j, mW + (size_t)l * F + j, vW + (size_t)l * F + j, (float)acc[l], a);
+            } else {
+                const int l = j / w;
+                double acc = 0.0;
+#pragma unroll 4
+                for (int r = 0; r < bs; ++r) {
+                    float xv = Xc[(size_t)pr[r] * pb.ldx + j];
+                    if (drop) xv *= dropout_scale(seed, pb.stream_id, (uint32_t)r * (uint32_t)F + (uint32_t)j, p, inv_keep);
+                    acc = fma((double)gs[r * LP + l], (double)xv, acc);
+                }
+                adamw(Wp + j, mW + j, vW + j, (float)acc, a);
+            }
+        }
+        if (tid < L) {
+            double acc = 0.0;
+            for (int r = 0; r < bs; ++r) acc += (double)gs[r * LP + tid];
+            adamw(pb.b + tid, pb.mb + tid, pb.vb + tid, (float)acc, a);
+        }
+        __syncthreads();                                                     // W, b of this step before the next step's logits
+    }
+    if (ONCHIP)
+        for (int e = tid; e < nW; e += HT_THREADS) {
+            pb.W[e] = Wp[e];
+            pb.mW[e] = mW[e];
+            pb.vW[e] = vW[e];
+        }
+    if (tid == 0) {
+        pb.t[0] = t0 + pb.S;
+        pb.loss_out[0] = run_l;
+        pb.loss_out[1] = run_v;
+    }
+}
+
+__global__ __launch_bounds__(HT_THREADS) void head_train_epoch_kernel(const MedpHeadProblem* __restrict__ tab) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char head_smem[];
+    __shared__ double red[HT_WAVES];
+    const MedpHeadProblem pb = tab[blockIdx.x];
+    const int tid = threadIdx.x;
+    // a permutation entry outside [0, N) is never dereferenced: the problem's outputs become NaN
+    int bad = 0;
+    for (int i = tid; i < pb.S * pb.bs; i += HT_THREADS) bad |= (unsigned)pb.perm[i] >= (unsigned)pb.N;
+    if (__syncthreads_or(bad)) {
+        const int nW = (int)head_nw(pb.F, pb.L, pb.label_width);
+        for (int e = tid; e < nW; e += HT_THREADS) pb.W[e] = kNaNf;
+        if (tid < pb.L) pb.b[tid] = kNaNf;
+        if (tid == 0) pb.loss_out[0] = pb.loss_out[1] = (double)kNaNf;
+        return;
+    }
+    float* gs = (float*)head_smem;
+    const int lp = head_lp(pb.L);
+    float* st = gs + pb.bs * lp;
+    const bool on = head_onchip(pb.F, pb.L, pb.label_width, pb.bs);          // uniform over the workgroup
+    if (lp == 2) {
+        if (on) head_epoch<2, true>(pb, gs, st, red);
+        else head_epoch<2, false>(pb, gs, st, red);
+    } else if (lp == 8) {
+        if (on) head_epoch<8, true>(pb, gs, st, red);
+        else head_epoch<8, false>(pb, gs, st, red);
+    } else {
+        if (on) head_epoch<16, true>(pb, gs, st, red);
+        else head_epoch<16, false>(pb, gs, st, red);
+    }
+}
+
+// grid (ceil(n / HS_ROWS)); wave per row
+template <int LP>
+__device__ __forceinline__ void head_scores_rows(const float* __restrict__ X, long long ldx, int N, int col0, int F, int L, int w,
+                                                 const float* __restrict__ W, const float* __restrict__ b, const int* __restrict__ rows,
+                                                 int n, float* __restrict__ logits, double* __restrict__ probs) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i0 = blockIdx.x * HS_ROWS;
+    for (int i = i0 + wave; i < min(i0 + HS_ROWS, n); i += HS_WAVES) {
+        const int row = rows ? rows[i] : i;
+        const bool ok = (unsigned)row < (unsigned)N;
+        double z = 0.0;
+        if (ok) {
+            const float* xr = X + (size_t)row * ldx + col0;
+            if (w == 0) {
+                double acc[LP];
+                row_dots<LP>(xr, W, F, L, lane, false, 0u, 0u, 0u, 0.f, 1.f, acc);
+#pragma unroll
+                for (int l = 0; l < LP; ++l)
+                    if (lane == l) z = acc[l];
+            } else if (lane < L) {
+                for (int k = 0; k < w; ++k) z = fma((double)xr[lane * w + k], (double)W[lane * w + k], z);
+            }
+        }
+        if (lane < L) {
+            const float zf = ok ? (float)(z + (double)b[lane]) : kNaNf;
+            logits[(size_t)i * L + lane] = zf;
+            probs[(size_t)lane * n + i] = (double)(1.0f / (1.0f + expf(-zf)));
+        }
+    }
+}
+
+__global__ __launch_bounds__(HS_THREADS) void head_scores_kernel(const float* __restrict__ X, long long ldx, int N, int col0, int F, int L,
+                                                                  int w, const float* __restrict__ W, const float* __restrict__ b,
+                                                                  const int* __restrict__ rows, int n, float* __restrict__ logits,
+                                                                  double* __restrict__ probs) {
+    const int lp = head_lp(L);
+    if (lp == 2) head_scores_rows<2>(X, ldx, N, col0, F, L, w, W, b, rows, n, logits, probs);
+    else if (lp == 8) head_scores_rows<8>(X, ldx, N, col0, F, L, w, W, b, rows, n, logits, probs);
+    else head_scores_rows<16>(X, ldx, N, col0, F, L, w, W, b, rows, n, logits, probs);
+}
+
+int check_head_shape(const char* what, int p, long long ldx, int N, int ldy, int col0, int F, int L, int w) {
+    MEDP_CHECK_ARG(F >= 1 && F <= MEDP_HEAD_MAX_F, "%s: problem %d has F=%d, not in [1, %d]", what, p, F, MEDP_HEAD_MAX_F);
+    MEDP_CHECK_ARG(L >= 1 && L <= MEDP_HEAD_MAX_L, "%s: problem %d has L=%d, not in [1, %d]", what, p, L, MEDP_HEAD_MAX_L);
+    MEDP_CHECK_ARG(w >= 0 && (w == 0 || (long long)L * w == F), "%s: problem %d has label_width=%d with L=%d, F=%d (F = L label_width is needed)",
+                   what, p, w, L, F);
+    MEDP_CHECK_ARG(N >= 1 && col0 >= 0 && (long long)col0 + F <= ldx, "%s: problem %d columns [%d, %lld) leave a row of %lld (N=%d)", what, p,
+                   col0, (long long)col0 + F, ldx, N);
+    MEDP_CHECK_ARG(ldy < 0 || ldy >= L, "%s: problem %d has ldy=%d < L=%d", what, p, ldy, L);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int medp_head_train_onchip(int F, int L, int label_width, int bs) {
+    if (F < 1 || L < 1 || L > MEDP_HEAD_MAX_L || label_width < 0 || bs < 1) return 0;
+    return head_onchip(F, L, label_width, bs) ? 1 : 0;
+}
+
+extern "C" int medp_head_train_epoch(const MedpHeadProblem* table_host, const MedpHeadProblem* table_dev, int P, void* stream) {
+    MEDP_CHECK_ARG(table_host, "head_train_epoch: null host table");
+    MEDP_CHECK_ARG(P >= 1 && P <= 65535, "head_train_epoch: P=%d is not in [1, 65535]", P);
+    long long lds = 0;
+    for (int p = 0; p < P; ++p) {
+        const MedpHeadProblem& q = table_host[p];
+        MEDP_CHECK_ARG(q.X && q.Y && q.M && q.W && q.b && q.mW && q.vW && q.mb && q.vb && q.t && q.perm && q.loss_out,
+                       "head_train_epoch: problem %d has a null pointer", p);
+        MEDP_TRY(check_head_shape("head_train_epoch", p, q.ldx, q.N, q.ldy, q.col0, q.F, q.L, q.label_width));
+        MEDP_CHECK_ARG(q.bs >= 1 && q.bs <= MEDP_HEAD_MAX_BS, "head_train_epoch: problem %d has bs=%d, not in [1, %d]", p, q.bs,
+                       MEDP_HEAD_MAX_BS);
+        MEDP_CHECK_ARG(q.S >= 1 && (long long)q.S * q.bs <= q.N, "head_train_epoch: problem %d has S=%d steps of %d rows with N=%d", p, q.S,
+                       q.bs, q.N);
+        MEDP_CHECK_ARG(q.dropout_p >= 0.f && q.dropout_p < 1.f, "head_train_epoch: problem %d has dropout_p=%g, not in [0, 1)", p,
+                       (double)q.dropout_p);
+        MEDP_CHECK_ARG(q.lr >= 0.0 && q.beta1 >= 0.0 && q.beta1 < 1.0 && q.beta2 >= 0.0 && q.beta2 < 1.0 && q.eps >= 0.0,
+                       "head_train_epoch: problem %d has bad AdamW scalars", p);
+        long long need = head_g_bytes(q.L, q.bs);
+        if (head_onchip(q.F, q.L, q.label_width, q.bs)) need += 12 * head_nw(q.F, q.L, q.label_width);
+        lds = need > lds ? need : lds;
+    }
+    MEDP_CHECK_ARG(table_dev, "head_train_epoch: null device table");      // after the checks: the host copy alone can be validated
+    MEDP_ONCE_PER_DEVICE({
+        hipFuncSetAttribute((const void*)head_train_epoch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, HEAD_LDS_BUDGET);
+    });
+    head_train_epoch_kernel<<<P, HT_THREADS, (size_t)lds, (hipStream_t)stream>>>(table_dev);
+    MEDP_LAUNCH_CHECK("medp_head_train_epoch");
+    return 0;
+}
+
+extern "C" int medp_head_scores(const float* X, long long ldx, int N, int col0, int F, int L, int label_width, const float* W,
+                                const float* b, const int* rows, int n, float* logits, double* probs, void* stream) {
+    MEDP_CHECK_ARG(X && W && b && logits && probs, "head_scores: null argument");
+    MEDP_TRY(check_head_shape("head_scores", 0, ldx, N, -1, col0, F, L, label_width));
+    MEDP_CHECK_ARG(n >= 1, "head_scores: n=%d < 1", n);
+    head_scores_kernel<<<(n + HS_ROWS - 1) / HS_ROWS, HS_THREADS, 0, (hipStream_t)stream>>>(X, ldx, N, col0, F, L, label_width, W, b, rows, n,
+                                                                                          logits, probs);
+    MEDP_LAUNCH_CHECK("medp_head_scores");
+    return 0;
+}

@@ -1,0 +1,213 @@
+"""Logit-level fusion probe (reference analysis/logit_fusion_probe.py): does adding the time-series logits to the image logits help?
+Stage 1 trains a linear probe on the frozen image features, stage 2 one on the frozen DuETT features, stage 3 a small fusion head on
+the two heads' logits.
+
+    python -m multimodal_edema_prediction_amd.logit_fusion_probe --ts_modality duett_multiscale --fusion_type per_label
+
+The reference's names, positional signatures and state-dict keys.  Stages 1 and 2 are independent and share one launch group
+(`unimodal_linear_probe.train_linear_heads`); the fusion head maps onto the same kernel (head_probe.py):
+    linear     a dense problem on cat(img, ts) [N, 2L], no dropout          (head.weight / head.bias)
+    per_label  label_width = 2 on the interleaved [N, L, 2] layout, initialised w_img = 1, w_ts = 0, b = 0
+               (per_label_w / per_label_b)
+    mlp        no kernel: the eager loop of `head_probe.eager_fit`, NOT accelerated (as is a `duett_attn_pool` stage 2).
+`main()` runs on `SyntheticCohort` with the synthetic encoders.  Without a GPU the trainers raise (no CPU fallback)."""
+from __future__ import annotations
+
+import argparse
+import os
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import head_probe
+from .abi import require_gpu
+from .unimodal_linear_probe import (DEFAULTS, LinearHead, _cohort_args, _eval_multi, _extract_cxr, _extract_duett,  # noqa: F401
+                                    _extract_modality, _logits, _report, _select_labels, _table_from_logits, _train_eager, masked_bce,
+                                    train_linear_head, train_linear_heads)
+
+
+class LogitFusionHead(nn.Module):
+    """(img_logits, ts_logits) [B, L] each -> fused logits [B, L].  linear: Linear(2L, L) on the concatenation; mlp: Linear(2L, hidden)
+    -> GELU -> Dropout -> Linear(hidden, L); per_label: fused[k] = w[k, 0] img[k] + w[k, 1] ts[k] + b[k], starting at the image
+    logit itself (w = (1, 0), b = 0)."""
+
+    def __init__(self, n_labels: int, fusion_type: str = "linear", hidden: int = 32, dropout: float = 0.1):
+        super().__init__()
+        self.fusion_type, self.n_labels = fusion_type, n_labels
+        if fusion_type == "linear":
+            self.head = nn.Linear(2 * n_labels, n_labels)
+        elif fusion_type == "mlp":
+            self.head = nn.Sequential(nn.Linear(2 * n_labels, hidden), nn.GELU(), nn.Dropout(dropout), nn.Linear(hidden, n_labels))
+        elif fusion_type == "per_label":
+            w = torch.zeros(n_labels, 2)
+            w[:, 0] = 1.0
+            self.per_label_w = nn.Parameter(w)
+            self.per_label_b = nn.Parameter(torch.zeros(n_labels))
+        else:
+            raise ValueError(f"unknown fusion_type={fusion_type!r}")
+
+    def forward(self, logits_img: torch.Tensor, logits_ts: torch.Tensor) -> torch.Tensor:
+        if self.fusion_type == "per_label":
+            return (torch.stack([logits_img, logits_ts], dim=-1) * self.per_label_w).sum(dim=-1) + self.per_label_b
+        return self.head(torch.cat([logits_img, logits_ts], dim=-1))
+
+
+def _fusion_inputs(img: torch.Tensor, ts: torch.Tensor, fusion_type: str) -> torch.Tensor:
+    """The [N, 2L] matrix the kernel reads: (img | ts) for linear, (img_0, ts_0, img_1, ts_1, ..) for per_label."""
+    if fusion_type == "per_label":
+        return torch.stack([img, ts], dim=-1).reshape(img.shape[0], -1).contiguous()
+    return torch.cat([img, ts], dim=-1).contiguous()
+
+
+def train_fusion_head(img_tr, ts_tr, Y_tr, M_tr, img_va, ts_va, Y_va, M_va, label_names, device, fusion_type: str = "linear",
+                      hidden: int = 32, dropout: float = 0.1, epochs: int = 300, batch_size: int = 128, lr: float = 1e-3,
+                      weight_decay: float = 1e-4, verbose: bool = True, *, seed: int = 0, history=None, init_state=None):
+    """Fusion head on the two heads' logits -> (model on the device with the best-validation-macro-AUROC state, best epoch, value).
+    Keyword-only extras as in `train_linear_head`."""
+    L = len(label_names)
+    model = LogitFusionHead(n_labels=L, fusion_type=fusion_type, hidden=hidden, dropout=dropout)
+    if init_state is not None:
+        model.load_state_dict(init_state)
+    if fusion_type == "mlp":
+        return _train_eager(model, lambda m, a, b: m(a, b), [img_tr, ts_tr], Y_tr, M_tr, [img_va, ts_va], Y_va, M_va, device, epochs,
+                            batch_size, lr, weight_decay, verbose, history, tag="ep")
+    require_gpu()
+    device = torch.device(device)
+    to = lambda t: torch.as_tensor(t).to(device).float()  # noqa: E731
+    perms = head_probe.draw_epoch_permutations(img_tr.shape[0], epochs)
+    W, b, width = ((model.per_label_w, model.per_label_b, 2) if fusion_type == "per_label" else (model.head.weight, model.head.bias, 0))
+    problem = head_probe.HeadProblem(_fusion_inputs(to(img_tr), to(ts_tr), fusion_type), to(Y_tr), to(M_tr), W, b, label_width=width,
+                                     bs=batch_size, lr=lr, weight_decay=weight_decay, dropout=0.0, seed=seed)
+    val = (_fusion_inputs(to(img_va), to(ts_va), fusion_type), to(Y_va), to(M_va))
+    res = head_probe.train_heads([problem], [val], epochs, [perms],
+                                 record_val_logits=bool(history is not None and history.get("record_val_logits")))[0]
+    keys = ("per_label_w", "per_label_b") if fusion_type == "per_label" else ("head.weight", "head.bias")
+    model.load_state_dict({keys[0]: res["best_W"].reshape(W.shape), keys[1]: res["best_b"]})
+    model.to(device)
+    _report(res, history, verbose, tag="ep")
+    return model, res["best_epoch"], res["best_val"]
+
+
+def _eval_from_logits(logits, Y, M, label_names: list) -> dict:
+    """logits / Y / M [N, L] (device tensors or arrays) -> per-label AUROC / AUPRC over the known rows, and their macro means."""
+    return _table_from_logits(logits, Y, M, label_names)
+
+
+@torch.no_grad()
+def _head_logits(model, X: torch.Tensor, device, batch_size: int = 512) -> torch.Tensor:
+    """[N, L] fp32 logits of a LinearHead on the device (the scores kernel; `batch_size` only chunks the eager attention-pool path)."""
+    return _logits(model, X, device)
+
+
+def _load_or_extract_features(args, device) -> dict:
+    """{img_tr/va/te, ts_tr/va/te: device tensors, labels: {split: (Y, M)}}; X_cxr_<split>.npy / X_<ts_modality>_<split>.npy of
+    --features_dir (written by unimodal_linear_probe --save_features) are reused when all three splits are there."""
+    fd, out = args.features_dir, {}
+    short = {"train": "tr", "val": "va", "test": "te"}
+    for key, modality in (("img", "cxr"), ("ts", args.ts_modality)):
+        paths = {s: os.path.join(fd, f"X_{modality}_{s}.npy") for s in short} if fd else {}
+        if fd and all(os.path.exists(p) for p in paths.values()):
+            print(f"[cache] loading {modality} features from {fd}")
+            for s, p in paths.items():
+                out[f"{key}_{short[s]}"] = torch.as_tensor(np.load(p)).float().to(device)
+        else:
+            print(f"[extract] {modality} - frozen forward")
+            feats, labels = _extract_modality(args, modality, device)
+            out["labels"] = labels
+            for s in short:
+                out[f"{key}_{short[s]}"] = feats[s]
+    if "labels" not in out:
+        from .unimodal_linear_probe import _extract_labels, _loaders
+        out["labels"] = {s: _extract_labels(dl, device) for s, dl in _loaders(args, "student").items()}
+    return out
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Logit-level fusion probe (frozen unimodal backbones)")
+    _cohort_args(p)
+    p.add_argument("--features_dir", default="", help="a unimodal_linear_probe --save_features folder: reused when complete")
+    p.add_argument("--ts_modality", default="duett_multiscale", choices=["duett_rep", "duett_hourly_mean", "duett_multiscale", "duett_attn_pool"])
+    p.add_argument("--uni_epochs", type=int, default=300)
+    p.add_argument("--uni_lr", type=float, default=1e-4)
+    p.add_argument("--uni_weight_decay", type=float, default=1e-4)
+    p.add_argument("--uni_batch_size", type=int, default=128)
+    p.add_argument("--uni_dropout", type=float, default=0.1)
+    p.add_argument("--fusion_type", default="linear", choices=["per_label", "linear", "mlp"])
+    p.add_argument("--fusion_hidden", type=int, default=32)
+    p.add_argument("--fusion_dropout", type=float, default=0.1)
+    p.add_argument("--fus_epochs", type=int, default=300)
+    p.add_argument("--fus_lr", type=float, default=1e-3)
+    p.add_argument("--fus_weight_decay", type=float, default=1e-4)
+    p.add_argument("--fus_batch_size", type=int, default=128)
+    p.add_argument("--quiet", action="store_true", help="no per-epoch lines")
+    return p.parse_args(argv)
+
+
+def main(argv=None) -> dict:
+    args = parse_args(argv)
+    require_gpu()
+    device = torch.device("cuda", torch.cuda.current_device())
+    print(f"[device] {device}")
+    print(f"[config] ts_modality={args.ts_modality}  fusion_type={args.fusion_type}")
+    torch.manual_seed(args.seed)
+    label_cols, cols = _select_labels(args.labels)
+    feats = _load_or_extract_features(args, device)
+    print(f"[multi-label] L={len(label_cols)} labels: {label_cols}")
+    (Y_tr, M_tr), (Y_va, M_va), (Y_te, M_te) = ((y[:, cols].contiguous(), m[:, cols].contiguous()) for y, m in
+                                                (feats["labels"][s] for s in ("train", "val", "test")))
+    X_img_tr, X_img_va, X_img_te = feats["img_tr"], feats["img_va"], feats["img_te"]
+    X_ts_tr, X_ts_va, X_ts_te = feats["ts_tr"], feats["ts_va"], feats["ts_te"]
+    print(f"[shape] img feat d={X_img_tr.shape[-1]}   ts feat d={X_ts_tr.shape[-1]}" + (f" (T={X_ts_tr.shape[1]})" if X_ts_tr.ndim == 3 else ""))
+    verbose = not args.quiet
+    uni = dict(label_names=label_cols, device=device, epochs=args.uni_epochs, batch_size=args.uni_batch_size, lr=args.uni_lr,
+               weight_decay=args.uni_weight_decay, dropout=args.uni_dropout, verbose=verbose, seed=args.seed)
+    use_attn_pool = args.ts_modality == "duett_attn_pool"
+    if use_attn_pool:
+        print("\n[stage 1] CXR linear probe")
+        cxr_head, ep_c, val_c = train_linear_head(X_img_tr, Y_tr, M_tr, X_img_va, Y_va, M_va, **uni)
+        print(f"\n[stage 2] DuETT linear probe ({args.ts_modality})")
+        ts_head, ep_t, val_t = train_linear_head(X_ts_tr, Y_tr, M_tr, X_ts_va, Y_va, M_va, use_attn_pool=True, **uni)
+    else:
+        print(f"\n[stage 1 + 2] CXR linear probe and DuETT linear probe ({args.ts_modality}): one launch group")
+        (cxr_head, ep_c, val_c), (ts_head, ep_t, val_t) = train_linear_heads([X_img_tr, X_ts_tr], Y_tr, M_tr, [X_img_va, X_ts_va], Y_va, M_va,
+                                                                           **uni)
+    print(f"[stage 1] best epoch={ep_c}  val macro AUROC={val_c:.4f}")
+    print(f"[stage 2] best epoch={ep_t}  val macro AUROC={val_t:.4f}")
+    img_l = {s: _head_logits(cxr_head, X, device) for s, X in (("tr", X_img_tr), ("va", X_img_va), ("te", X_img_te))}
+    ts_l = {s: _head_logits(ts_head, X, device) for s, X in (("tr", X_ts_tr), ("va", X_ts_va), ("te", X_ts_te))}
+    img_res_te = _eval_from_logits(img_l["te"], Y_te, M_te, label_cols)
+    ts_res_te = _eval_from_logits(ts_l["te"], Y_te, M_te, label_cols)
+    print(f"\n[stage 3] fusion head ({args.fusion_type}) on concat logits")
+    fusion, ep_f, val_f = train_fusion_head(img_l["tr"], ts_l["tr"], Y_tr, M_tr, img_l["va"], ts_l["va"], Y_va, M_va, label_names=label_cols,
+                                            device=device, fusion_type=args.fusion_type, hidden=args.fusion_hidden,
+                                            dropout=args.fusion_dropout, epochs=args.fus_epochs, batch_size=args.fus_batch_size,
+                                            lr=args.fus_lr, weight_decay=args.fus_weight_decay, verbose=verbose, seed=args.seed)
+    print(f"[stage 3] best epoch={ep_f}  val macro AUROC={val_f:.4f}")
+    fusion.eval()
+    with torch.no_grad():
+        fus_logits_te = fusion(img_l["te"], ts_l["te"])
+    fus_res_te = _eval_from_logits(fus_logits_te, Y_te, M_te, label_cols)
+    print(f"\n[result] logit-fusion probe   (fusion_type={args.fusion_type})")
+    hdr = (f"  {'label':<22} {'n':>6} {'pos':>6}   {'img_roc':>8} {'ts_roc':>8} {'fus_roc':>8}   {'img_prc':>8} {'ts_prc':>8} {'fus_prc':>8}")
+    print(hdr)
+    print("  " + "-" * (len(hdr) - 2))
+    for name in label_cols:
+        i, t, f = img_res_te["per_label"][name], ts_res_te["per_label"][name], fus_res_te["per_label"][name]
+        print(f"  {name:<22} {i['n']:>6d} {i['pos']:>6d}   {i['auroc']:>8.4f} {t['auroc']:>8.4f} {f['auroc']:>8.4f}   "
+              f"{i['auprc']:>8.4f} {t['auprc']:>8.4f} {f['auprc']:>8.4f}")
+    print("  " + "-" * (len(hdr) - 2))
+    print(f"  {'macro':<22} {'':>6} {'':>6}   {img_res_te['macro_auroc']:>8.4f} {ts_res_te['macro_auroc']:>8.4f} "
+          f"{fus_res_te['macro_auroc']:>8.4f}   {img_res_te['macro_auprc']:>8.4f} {ts_res_te['macro_auprc']:>8.4f} "
+          f"{fus_res_te['macro_auprc']:>8.4f}")
+    if args.fusion_type == "per_label":
+        print("\n[per_label weights]  (init: w_img=1, w_ts=0, b=0)")
+        w, b = fusion.per_label_w.detach().cpu().numpy(), fusion.per_label_b.detach().cpu().numpy()
+        print(f"  {'label':<22} {'w_img':>8} {'w_ts':>8} {'bias':>8}")
+        for k, name in enumerate(label_cols):
+            print(f"  {name:<22} {w[k, 0]:>8.4f} {w[k, 1]:>8.4f} {b[k]:>8.4f}")
+    return {"img": img_res_te, "ts": ts_res_te, "fusion": fus_res_te, "best_epochs": (ep_c, ep_t, ep_f), "model": fusion}
+
+
+if __name__ == "__main__":
+    main()

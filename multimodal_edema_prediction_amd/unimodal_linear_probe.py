@@ -1,0 +1,373 @@
+"""Unimodal linear probes (reference analysis/unimodal_linear_probe.py): how good is each modality alone?  A joint multi-label
+`Dropout -> Linear` head is trained on the frozen features of ONE modality with minibatch AdamW and selected on validation macro AUROC.
+
+    python -m multimodal_edema_prediction_amd.unimodal_linear_probe --modality cxr
+    python -m multimodal_edema_prediction_amd.unimodal_linear_probe --modality duett_multiscale
+
+The reference's names, positional signatures and state-dict keys.  What differs:
+  * the features stay on the device as one fp32 tensor per split (`_extract_*` return device tensors, not numpy arrays);
+  * `train_linear_head` runs every step of an epoch in one `medp_head_train_epoch` launch and selects on the device (head_probe.py);
+    the initial parameters and every epoch's row order are drawn on the host exactly as the reference's module and DataLoader
+    draw them, the dropout masks come from the library's counter hash (`seed`);
+  * `duett_attn_pool` (a learned attention pooling over [N, T, d]) has no kernel: it runs the reference's eager loop through torch
+    autograd on the device (`head_probe.eager_fit`), NOT accelerated;
+  * `main()` runs on `SyntheticCohort` with the synthetic encoders, as train_synthetic does (the MIMIC files are not available).
+Without a GPU the trainers raise (no CPU fallback)."""
+from __future__ import annotations
+
+import argparse
+import os
+from typing import Sequence
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import evaluator, head_probe
+from .abi import require_gpu
+from .cohort import PATHOLOGY_LABELS, CohortCfg, SyntheticCohort, collate
+from .cxr import CXREncoder
+from .duett import load_duett_backbone
+from .raw_trajectory_probe import METRICS_MAX_LEN
+
+DEFAULTS = {"duett_ckpt": "synthetic", "cxr_model_name": "synthetic"}
+FEATURE_TYPES = ("rep", "hourly_mean", "multiscale", "attn_pool")
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# feature extraction: one frozen forward per batch, everything stays on the device
+# ------------------------------------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def _extract_cxr(loader, model, device):
+    """(features [N, d] fp32, y [N]) on the device: the CLS token of the frozen image encoder."""
+    model.eval()
+    feats, labels = [], []
+    for batch in loader:
+        out = model(batch["pixel_values"].to(device, non_blocking=True))
+        cls = out[0] if isinstance(out, tuple) else out
+        feats.append(cls.detach().float())
+        labels.append(batch["y"].float().to(device))
+    return torch.cat(feats).contiguous(), torch.cat(labels)
+
+
+def _pool_duett_tokens(tokens: torch.Tensor, feature_type: str) -> torch.Tensor:
+    """tokens [B, T+1, d] = (hour 0 .. hour T-1, REP) -> the feature of `feature_type`:
+    rep [B, d]; hourly_mean [B, d]; multiscale [B, 4d] = means over the first quarter, the second quarter and the second half of
+    the hours, then REP; attn_pool [B, T, d] (the hourly tokens; the head pools them)."""
+    hourly, rep = tokens[:, :-1, :], tokens[:, -1, :]
+    if feature_type == "rep":
+        return rep
+    if feature_type == "hourly_mean":
+        return hourly.mean(dim=1)
+    if feature_type == "multiscale":
+        T = hourly.shape[1]
+        q1, q2 = T // 4, T // 2
+        parts = [hourly[:, :q1, :].mean(dim=1), hourly[:, q1:q2, :].mean(dim=1), hourly[:, q2:, :].mean(dim=1), rep]
+        return torch.cat(parts, dim=-1)
+    if feature_type == "attn_pool":
+        return hourly
+    raise ValueError(f"unknown feature_type={feature_type!r}; expected one of {set(FEATURE_TYPES)}")
+
+
+@torch.no_grad()
+def _extract_duett(loader, backbone, device, feature_type: str):
+    """(features fp32, y [N]) on the device: the pooled tokens of the frozen DuETT backbone."""
+    backbone.eval()
+    feats, labels = [], []
+    for batch in loader:
+        x = tuple(tuple(t.to(device, non_blocking=True) for t in batch[k]) for k in ("x_ts", "x_static", "bin_ends"))
+        y = batch["y"].float()
+        tokens = backbone.encode(backbone.feats_to_input(x, y.shape[0]))                  # [B, T+1, d_rep]
+        if isinstance(tokens, tuple):                                                      # a backbone that also returns psi
+            tokens = tokens[0]
+        feats.append(_pool_duett_tokens(tokens, feature_type).detach().float())
+        labels.append(y.to(device))
+    return torch.cat(feats).contiguous(), torch.cat(labels)
+
+
+@torch.no_grad()
+def _extract_labels(loader, device):
+    """(Y, M) [N, L] fp32 on the device from the batches' y_multi / y_multi_mask."""
+    Y = torch.cat([b["y_multi"].float() for b in loader]).to(device)
+    M = torch.cat([b["y_multi_mask"].float() for b in loader]).to(device)
+    return Y.contiguous(), M.contiguous()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the head
+# ------------------------------------------------------------------------------------------------------------------------------
+class LinearHead(nn.Module):
+    """`Dropout -> Linear` (state-dict keys head.1.weight / head.1.bias).  use_attn_pool: the input is [B, T, d] and is first
+    pooled over T with softmax(x . attn_query / sqrt(d)) weights, the query being learned with the head."""
+
+    def __init__(self, d_in: int, num_labels: int, dropout: float = 0.1, use_attn_pool: bool = False):
+        super().__init__()
+        self.use_attn_pool = use_attn_pool
+        if use_attn_pool:
+            self.attn_query = nn.Parameter(torch.randn(d_in) * 0.02)
+        self.head = nn.Sequential(nn.Dropout(dropout), nn.Linear(d_in, num_labels))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.use_attn_pool:
+            w = torch.softmax((x @ self.attn_query) / (x.shape[-1] ** 0.5), dim=1)
+            x = (x * w.unsqueeze(-1)).sum(dim=1)
+        return self.head(x)
+
+
+def masked_bce(logits: torch.Tensor, labels: torch.Tensor, label_mask: torch.Tensor) -> torch.Tensor:
+    """Mean BCE-with-logits over the known labels of the batch (no pos_weight); zero, with a graph, when none is known."""
+    return head_probe.masked_bce_loss(logits, labels, label_mask)
+
+
+@torch.no_grad()
+def _scores(model, X: torch.Tensor, device):
+    """([N, L] fp32 logits, [N, L] fp32 probabilities) on the device: the scores kernel for a plain `Dropout -> Linear` head, the
+    module's forward (and 1 / (1 + exp(-z)) in fp32) otherwise."""
+    model.eval()
+    X = X.to(device)
+    if isinstance(model, LinearHead) and not model.use_attn_pool:
+        lin = model.head[1]
+        z, p = head_probe.head_scores(X.float(), lin.weight.detach().float(), lin.bias.detach().float())
+        return z, p.t().float()                                                        # the kernel's fp32 sigmoid, widened: exact back
+    z = torch.cat([model(X[i:i + 512]).float() for i in range(0, X.shape[0], 512)])
+    return z, 1.0 / (1.0 + torch.exp(-z))
+
+
+def _logits(model, X: torch.Tensor, device) -> torch.Tensor:
+    return _scores(model, X, device)[0]
+
+
+def _table_from_logits(logits: torch.Tensor, Y, M, label_names: Sequence[str], probs=None) -> dict:
+    """Per-label AUROC / AUPRC of the fp32 sigmoid over the label's known rows, and the macro means over the defined ones.  On the
+    device (one metrics launch) when every label's known rows fit the metrics kernel; otherwise on the host with one copy."""
+    z = torch.as_tensor(logits).float()
+    Y, M = torch.as_tensor(Y).float(), torch.as_tensor(M).float()
+    probs = 1.0 / (1.0 + torch.exp(-z)) if probs is None else probs                    # fp32, as the reference takes it
+    known = (M.cpu().numpy() > 0.5)
+    y_h = Y.cpu().numpy()
+    n_known = known.sum(0)
+    if z.is_cuda and n_known.max(initial=0) <= METRICS_MAX_LEN:
+        m = head_probe.LabelMetrics(Y.to(z.device), M.to(z.device))(probs.t().contiguous().double()).cpu().numpy()
+        au, pr = m[:, 1], m[:, 2]
+    else:
+        p_h = probs.cpu().numpy()
+        au = np.array([evaluator.auroc(y_h[known[:, i], i], p_h[known[:, i], i]) for i in range(len(label_names))])
+        pr = np.array([evaluator.average_precision(y_h[known[:, i], i], p_h[known[:, i], i]) for i in range(len(label_names))])
+    per_label, aurocs, auprcs = {}, [], []
+    for i, name in enumerate(label_names):
+        yk = y_h[known[:, i], i]
+        defined = n_known[i] >= 2 and len(np.unique(yk)) >= 2
+        per_label[name] = {"auroc": float(au[i]) if defined else float("nan"), "auprc": float(pr[i]) if defined else float("nan"),
+                           "n": int(n_known[i]), "pos": int(yk.sum())}
+        if defined:
+            aurocs.append(float(au[i]))
+            auprcs.append(float(pr[i]))
+    return {"per_label": per_label, "macro_auroc": float(np.mean(aurocs)) if aurocs else float("nan"),
+            "macro_auprc": float(np.mean(auprcs)) if auprcs else float("nan")}
+
+
+@torch.no_grad()
+def _eval_multi(model, X: torch.Tensor, Y: torch.Tensor, M: torch.Tensor, label_names: list, device) -> dict:
+    """model(X) -> per-label AUROC / AUPRC over the known rows, and their macro means."""
+    z, p = _scores(model, X, device)
+    return _table_from_logits(z, Y, M, label_names, probs=p)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# training
+# ------------------------------------------------------------------------------------------------------------------------------
+def _report(result: dict, history, verbose: bool, tag: str = "epoch") -> None:
+    if history is not None:
+        history.update(curve=result["curve"], train_loss=result["loss_sum"] / np.maximum(result["valid_sum"], 1),
+                       loss_sum=result["loss_sum"], valid_sum=result["valid_sum"])
+        if "val_logits" in result:
+            history["val_logits"] = result["val_logits"]
+    if verbose:
+        print("\n".join(head_probe.history_lines(result, tag)))
+
+
+def train_linear_heads(X_trs: Sequence[torch.Tensor], Y_tr, M_tr, X_vas: Sequence[torch.Tensor], Y_va, M_va, label_names, device, epochs: int = 100,
+                       batch_size: int = 128, lr: float = 1e-4, weight_decay: float = 1e-4, dropout: float = 0.1, verbose: bool = True, *,
+                       seed: int = 0, histories=None, init_states=None) -> list:
+    """`train_linear_head` for several feature sets over the same rows and labels (several modalities; the image head and the TS
+    head of the fusion probe) as ONE launch group: one `medp_head_train_epoch` launch per epoch serves them all.  The modules are
+    built and the row orders drawn one head after the other, so the default generator is consumed as by consecutive calls."""
+    require_gpu()
+    device = torch.device(device)
+    Y_tr, M_tr, Y_va, M_va = (t.to(device).float() for t in (Y_tr, M_tr, Y_va, M_va))
+    models, problems, vals, perms = [], [], [], []
+    for k, (X_tr, X_va) in enumerate(zip(X_trs, X_vas)):
+        model = LinearHead(X_tr.shape[-1], len(label_names), dropout=dropout)
+        if init_states is not None and init_states[k] is not None:
+            model.load_state_dict(init_states[k])
+        perms.append(head_probe.draw_epoch_permutations(X_tr.shape[0], epochs))
+        lin = model.head[1]
+        problems.append(head_probe.HeadProblem(X_tr.to(device).float(), Y_tr, M_tr, lin.weight, lin.bias, bs=batch_size, lr=lr,
+                                               weight_decay=weight_decay, dropout=dropout, seed=seed, stream_id=k))
+        vals.append((X_va.to(device).float(), Y_va, M_va))
+        models.append(model)
+    record = any(h is not None and h.get("record_val_logits") for h in (histories or []))
+    results = head_probe.train_heads(problems, vals, epochs, perms, record_val_logits=record)
+    out = []
+    for k, (model, res) in enumerate(zip(models, results)):
+        model.load_state_dict({"head.1.weight": res["best_W"], "head.1.bias": res["best_b"]})
+        model.to(device)
+        _report(res, None if histories is None else histories[k], verbose)
+        out.append((model, res["best_epoch"], res["best_val"]))
+    return out
+
+
+def _train_eager(model, forward, train, Y_tr, M_tr, val, Y_va, M_va, device, epochs, batch_size, lr, weight_decay, verbose, history, tag="epoch"):
+    """The shared eager path (attention pooling, the MLP fusion head): NOT accelerated."""
+    require_gpu()
+    device = torch.device(device)
+    perms = head_probe.draw_epoch_permutations(Y_tr.shape[0], epochs)
+    model.to(device)
+    res = head_probe.eager_fit(model, forward, [t.to(device).float() for t in train], Y_tr.to(device).float(), M_tr.to(device).float(),
+                               [t.to(device).float() for t in val], Y_va.to(device).float(), M_va.to(device).float(), epochs=epochs,
+                               batch_size=batch_size, lr=lr, weight_decay=weight_decay, perms=perms)
+    _report(res, history, verbose, tag)
+    return model, res["best_epoch"], res["best_val"]
+
+
+def train_linear_head(X_tr, Y_tr, M_tr, X_va, Y_va, M_va, label_names: list, device, epochs: int = 100, batch_size: int = 128,
+                      lr: float = 1e-4, weight_decay: float = 1e-4, dropout: float = 0.1, verbose: bool = True, use_attn_pool: bool = False,
+                      *, seed: int = 0, history=None, init_state=None):
+    """Joint multi-label linear head -> (model on the device with the best-validation-macro-AUROC state, best epoch, best value).
+    X_*: [N, d] (or [N, T, d] with use_attn_pool); Y_*: [N, L] with unknown labels as 0; M_*: [N, L], 1 = known.
+    seed: the dropout hash's seed; history: a dict that receives `curve`, `train_loss`, `loss_sum`, `valid_sum` per epoch (and
+    `val_logits` when it holds record_val_logits=True); init_state: a state dict loaded in place of the default initialisation.
+    verbose prints the reference's per-epoch lines after the run (the epoch loop never synchronises)."""
+    if use_attn_pool:
+        model = LinearHead(X_tr.shape[-1], len(label_names), dropout=dropout, use_attn_pool=True)
+        if init_state is not None:
+            model.load_state_dict(init_state)
+        return _train_eager(model, lambda m, x: m(x), [X_tr], Y_tr, M_tr, [X_va], Y_va, M_va, device, epochs, batch_size, lr, weight_decay,
+                            verbose, history)
+    return train_linear_heads([X_tr], Y_tr, M_tr, [X_va], Y_va, M_va, label_names, device, epochs, batch_size, lr, weight_decay, dropout,
+                              verbose, seed=seed, histories=[history], init_states=[init_state])[0]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# main
+# ------------------------------------------------------------------------------------------------------------------------------
+def _cohort_args(p: argparse.ArgumentParser) -> None:
+    """The synthetic cohort that stands in for the MIMIC files."""
+    p.add_argument("--duett_ckpt", default=DEFAULTS["duett_ckpt"])
+    p.add_argument("--cxr_model_name", default=DEFAULTS["cxr_model_name"])
+    p.add_argument("--labels", default="all", help="comma-separated label columns, or 'all'")
+    p.add_argument("--n_timesteps", type=int, default=24)
+    p.add_argument("--n_vars", type=int, default=48)
+    p.add_argument("--d_static", type=int, default=8)
+    p.add_argument("--image_size", type=int, default=224)
+    p.add_argument("--n_train", type=int, default=4096)
+    p.add_argument("--n_val", type=int, default=1024)
+    p.add_argument("--n_test", type=int, default=1024)
+    p.add_argument("--split_seed", type=int, default=42)
+    p.add_argument("--batch_size", type=int, default=64, help="feature extraction (frozen backbone forward)")
+    p.add_argument("--num_workers", type=int, default=0)
+    p.add_argument("--seed", type=int, default=0, help="torch seed of the head initialisation / row orders and of the dropout hash")
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="CXR-only / DuETT-only linear probe")
+    p.add_argument("--modality", choices=["cxr", "duett", "duett_rep", "duett_hourly_mean", "duett_multiscale", "duett_attn_pool"],
+                   required=True, help="cxr: CLS token / duett_rep: [REP] token / duett_hourly_mean: mean of the hourly tokens / "
+                                       "duett_multiscale: three window means and REP / duett_attn_pool: hourly tokens with a learned "
+                                       "attention pooling (eager, not accelerated); 'duett' = duett_rep")
+    _cohort_args(p)
+    p.add_argument("--save_features", type=str, default="", help="a folder that receives X_<modality>_<split>.npy / y_<modality>_<split>.npy")
+    p.add_argument("--epochs", type=int, default=300)
+    p.add_argument("--lr", type=float, default=1e-4)
+    p.add_argument("--weight_decay", type=float, default=1e-4)
+    p.add_argument("--train_batch_size", type=int, default=128)
+    p.add_argument("--dropout", type=float, default=0.1)
+    return p.parse_args(argv)
+
+
+def _loaders(args, mode: str):
+    ccfg = CohortCfg(n_timesteps=args.n_timesteps, n_vars=args.n_vars, d_static=args.d_static, image_size=args.image_size,
+                     n_labels=len(PATHOLOGY_LABELS), seed=args.split_seed, learnable=True)
+    sizes = (("train", args.n_train, 0), ("val", args.n_val, 10_000_000), ("test", args.n_test, 20_000_000))
+    return {name: torch.utils.data.DataLoader(SyntheticCohort(ccfg, n, mode, off), batch_size=args.batch_size, shuffle=False,
+                                              num_workers=args.num_workers, collate_fn=lambda items: collate(items, mode))
+            for name, n, off in sizes}
+
+
+def _select_labels(requested: str):
+    """(names, column indices) of --labels within the cohort's label list."""
+    if requested.strip().lower() == "all":
+        return list(PATHOLOGY_LABELS), list(range(len(PATHOLOGY_LABELS)))
+    names = [c.strip() for c in requested.split(",") if c.strip()]
+    missing = [c for c in names if c not in PATHOLOGY_LABELS]
+    if missing:
+        raise ValueError(f"unknown label columns: {missing}")
+    return names, [PATHOLOGY_LABELS.index(c) for c in names]
+
+
+def _extract_modality(args, modality: str, device):
+    """{split: features} of one modality plus {split: (Y, M)}: frozen forwards over the three splits."""
+    include_cxr = modality == "cxr"
+    loaders = _loaders(args, "teacher" if include_cxr else "student")
+    if include_cxr:
+        enc = CXREncoder(model_name=args.cxr_model_name, freeze=True, return_patches=False).to(device)
+        feats = {s: _extract_cxr(dl, enc, device)[0] for s, dl in loaders.items()}
+    else:
+        backbone = load_duett_backbone(args.duett_ckpt, d_static_num=args.d_static, d_time_series_num=args.n_vars,
+                                       n_timesteps=args.n_timesteps, freeze=True).to(device)
+        feats = {s: _extract_duett(dl, backbone, device, modality[len("duett_"):])[0] for s, dl in loaders.items()}
+    labels = {s: _extract_labels(_loaders(args, "student")[s], device) for s in loaders}
+    return feats, labels
+
+
+def main(argv=None) -> dict:
+    args = parse_args(argv)
+    require_gpu()
+    device = torch.device("cuda", torch.cuda.current_device())
+    print(f"[device] {device}")
+    print(f"[modality] {args.modality.upper()}")
+    if args.modality == "duett":
+        args.modality = "duett_rep"
+    torch.manual_seed(args.seed)
+    label_cols, cols = _select_labels(args.labels)
+    print("\n[extract] frozen backbone forward on train/val/test")
+    feats, labels = _extract_modality(args, args.modality, device)
+    X_tr, X_va, X_te = feats["train"], feats["val"], feats["test"]
+    (Y_tr, M_tr), (Y_va, M_va), (Y_te, M_te) = ((y[:, cols].contiguous(), m[:, cols].contiguous()) for y, m in
+                                                (labels["train"], labels["val"], labels["test"]))
+    print(f"[shape] X_tr={tuple(X_tr.shape)}  X_va={tuple(X_va.shape)}  X_te={tuple(X_te.shape)}")
+    if args.save_features:
+        os.makedirs(args.save_features, exist_ok=True)
+        for name, X, y in (("train", X_tr, Y_tr), ("val", X_va, Y_va), ("test", X_te, Y_te)):
+            np.save(os.path.join(args.save_features, f"X_{args.modality}_{name}.npy"), X.cpu().numpy())
+            np.save(os.path.join(args.save_features, f"y_{args.modality}_{name}.npy"), y.cpu().numpy())
+        print(f"[save] features -> {args.save_features}")
+    print(f"[multi-label] evaluating {len(label_cols)} labels: {label_cols}")
+    use_attn_pool = args.modality == "duett_attn_pool"
+    pool_info = f", pool=attn (T={X_tr.shape[1]})" if use_attn_pool else ""
+    print(f"\n[train] joint multi-label linear head (d_feat={X_tr.shape[-1]}, L={len(label_cols)}{pool_info}, epochs={args.epochs}, "
+          f"lr={args.lr}, wd={args.weight_decay}, batch={args.train_batch_size}, dropout={args.dropout}, no pos_weight)")
+    model, best_epoch, best_val_macro = train_linear_head(X_tr, Y_tr, M_tr, X_va, Y_va, M_va, label_names=label_cols, device=device,
+                                                          epochs=args.epochs, batch_size=args.train_batch_size, lr=args.lr,
+                                                          weight_decay=args.weight_decay, dropout=args.dropout,
+                                                          use_attn_pool=use_attn_pool, seed=args.seed)
+    print(f"[train] best epoch={best_epoch}  best val macro AUROC={best_val_macro:.4f}")
+    tr_res = _eval_multi(model, X_tr, Y_tr, M_tr, label_cols, device)
+    va_res = _eval_multi(model, X_va, Y_va, M_va, label_cols, device)
+    te_res = _eval_multi(model, X_te, Y_te, M_te, label_cols, device)
+    print(f"\n[result] {args.modality.upper()}-only linear probe (joint multi-label)")
+    hdr = (f"  {'label':<25} {'train AUROC':>11} {'val AUROC':>10} {'test AUROC':>11} {'test AUPRC':>11} {'n_tr':>7} {'n_pos_tr':>10}")
+    print(hdr)
+    print("  " + "-" * (len(hdr) - 2))
+    for name in label_cols:
+        tr_s, va_s, te_s = tr_res["per_label"][name], va_res["per_label"][name], te_res["per_label"][name]
+        print(f"  {name:<25} {tr_s['auroc']:>11.4f} {va_s['auroc']:>10.4f} {te_s['auroc']:>11.4f} {te_s['auprc']:>11.4f} "
+              f"{tr_s['n']:>7d} {tr_s['pos']:>10d}")
+    print("  " + "-" * (len(hdr) - 2))
+    print(f"  {'macro average':<25} {tr_res['macro_auroc']:>11.4f} {va_res['macro_auroc']:>10.4f} {te_res['macro_auroc']:>11.4f} "
+          f"{te_res['macro_auprc']:>11.4f}")
+    return {"best_epoch": best_epoch, "best_val": best_val_macro, "train": tr_res, "val": va_res, "test": te_res, "model": model}
+
+
+if __name__ == "__main__":
+    main()
