@@ -9,6 +9,7 @@ import ctypes
 import os
 from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_uint, c_void_p
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -226,6 +227,19 @@ def ptr(t: torch.Tensor | None) -> int | None:
     if not t.is_cuda:
         raise RuntimeError("libmedp_hip operates on GPU memory only (tensor is on %s); there is no CPU fallback" % t.device)
     return t.data_ptr()
+
+
+def fp32_matrix(X: torch.Tensor, what: str):
+    """fp32 [N, ...] -> (contiguous tensor, N, row stride in elements) for the kernels that take a row-major matrix."""
+    if X.dtype != torch.float32:
+        raise TypeError(f"{what}: the probe kernels read fp32")
+    X = X.contiguous()
+    return X, X.shape[0], X.numel() // max(X.shape[0], 1)
+
+
+def table_bytes(host_array, count: int) -> np.ndarray:
+    """The first `count` entries of a ctypes problem table as a uint8 numpy copy (what goes to the device)."""
+    return np.frombuffer(host_array, dtype=np.uint8, count=ctypes.sizeof(host_array._type_) * count).copy()
 
 
 def require_gpu() -> None:

@@ -2,7 +2,9 @@
 csrc/cond_probe.hip: does the temporal branch (`ts_logits`, `ts_tokens`) say anything about a label once `img_logits` is known?
 
 The reference's names without the leading underscore and its return shapes; `run_probe` is the body of its `main()` label / probe
-loop (:440-574).  Per label four models are fitted on the probe-training split and scored on the test split:
+loop (:440-574); `bootstrap_differences`, `conditional_permutation` and `safe_metrics` are this probe's own draw or probability
+construction followed by a call into probe_stats.py, which all analysis probes share.  Per label four models are fitted on the
+probe-training split and scored on the test split:
     image_cal          sigmoid(a img + b)                              the control
     logit_add          sigmoid(a img + b ts + c)
     logit_interaction  logit_add + d img ts
@@ -14,8 +16,8 @@ iteration in well under ten steps.  All fit arithmetic is fp64; `functional.prec
 What runs where
   device, HIP   `probe_moments` (mean / scale of every column of every problem), `logistic_newton_terms` (objective, gradient and
                 Hessian of ALL problems of a width group in one launch group, standardising the teacher's fp32 outputs on the fly:
-                no standardised copy of the tokens exists), `probe_scores` (decision-function parts over any row list) and the
-                existing `resampled_binary_metrics` (BCE / AUROC / AUPRC of every bootstrap / permutation replicate).
+                no standardised copy of the tokens exists), `probe_scores` (decision-function parts over any row list) and
+                `probe_stats.resampled_binary_metrics` (BCE / AUROC / AUPRC of every bootstrap / permutation replicate).
   device, torch the teacher forwards of `gather`, the [N, K, 3] logit feature tensor (the product in fp32, as the reference takes it),
                 the sigmoid of the scores and the gather that builds the permuted probability vectors.
   host, numpy   the Newton driver: per iteration ONE copy of (f, g, H) and one batched `numpy.linalg.solve` (<= 10 iterations of a few
@@ -26,7 +28,6 @@ from __future__ import annotations
 
 import argparse
 import csv
-import ctypes
 import json
 import math
 import os
@@ -38,9 +39,9 @@ from typing import Dict, Mapping, Sequence
 import numpy as np
 import torch
 
-from .abi import MedpProbeProblem, check, lib, ptr, require_gpu, stream
-from .raw_trajectory_probe import (METRICS_MAX_LEN, _ci, _dev, _expit, _pearson, conditional_shuffle_indices, image_risk_bins,
-                                   resampled_binary_metrics)
+from .abi import MedpProbeProblem, check, fp32_matrix, lib, ptr, require_gpu, stream, table_bytes
+from .probe_stats import (METRICS_MAX_LEN, binary_metrics, draw_bootstrap_indices, draw_conditional_shuffles, expit, inference_fields,
+                          paired_bootstrap_gains, pearson, permutation_summary)
 
 F64 = torch.float64
 PROBE_NAMES = ("logit_add", "logit_interaction", "token_linear")
@@ -77,8 +78,7 @@ class ProblemTable:
         self.rows_total = offset
         self.max_rows = max([r.size for r in parts] + [0])
         self.row_off = np.cumsum([0] + [r.size for r in parts])
-        raw = np.frombuffer(self.host, dtype=np.uint8, count=ctypes.sizeof(MedpProbeProblem) * self.P).copy()
-        self.dev = torch.as_tensor(raw, device=device)
+        self.dev = torch.as_tensor(table_bytes(self.host, self.P), device=device)
         self.rows = torch.as_tensor(np.concatenate(parts) if parts else np.zeros(0, np.int32), device=device)
 
     def with_ranges(self, ranges: Sequence[tuple]) -> "ProblemTable":
@@ -89,22 +89,13 @@ class ProblemTable:
         for p, (j0, j1) in enumerate(ranges):
             q = self.host[p]
             t.host[p] = MedpProbeProblem(q.col_off, q.row_off, q.n_rows, q.F, q.y_col, int(j0), int(j1), 0)
-        raw = np.frombuffer(t.host, dtype=np.uint8, count=ctypes.sizeof(MedpProbeProblem) * self.P).copy()
-        t.dev = torch.as_tensor(raw, device=self.dev.device)
+        t.dev = torch.as_tensor(table_bytes(t.host, self.P), device=self.dev.device)
         return t
-
-
-def _matrix(X: torch.Tensor):
-    """fp32 [N, ...] contiguous -> (tensor, N, row stride in elements)."""
-    if X.dtype != torch.float32:
-        raise TypeError("the probe kernels read fp32 features")
-    X = X.contiguous()
-    return X, X.shape[0], X.numel() // max(X.shape[0], 1)
 
 
 def probe_moments(X: torch.Tensor, table: ProblemTable):
     """(mean, scale) [P, Fmax] fp64: `StandardScaler.fit` of every problem's columns over its rows."""
-    X, N, ldx = _matrix(X)
+    X, N, ldx = fp32_matrix(X, "X")
     mean = torch.empty((table.P, table.Fmax), dtype=F64, device=X.device)
     scale = torch.empty_like(mean)
     check(lib().medp_probe_moments(ptr(X), ldx, N, table.host, ptr(table.dev), ptr(table.rows), table.rows_total, ptr(mean), ptr(scale),
@@ -121,8 +112,8 @@ def terms_workspace(table: ProblemTable) -> torch.Tensor:
 
 def logistic_newton_terms(X, y, table: ProblemTable, theta, mean, scale, l2, hessian: bool = True, ws=None):
     """theta [P, Fmax+1] (standardised space, intercept last), l2 [P] -> (f [P], g [P, Fmax+1], H [P, Fmax+1, Fmax+1] or None)."""
-    X, N, ldx = _matrix(X)
-    y, Ny, ldy = _matrix(y)
+    X, N, ldx = fp32_matrix(X, "X")
+    y, Ny, ldy = fp32_matrix(y, "y")
     if Ny != N:
         raise ValueError(f"logistic_newton_terms: X has {N} rows, y {Ny}")
     for t in (theta, mean, scale, l2):
@@ -144,7 +135,7 @@ def logistic_newton_terms(X, y, table: ProblemTable, theta, mean, scale, l2, hes
 
 def probe_scores(X, table: ProblemTable, theta, mean, scale, intercept: bool = True) -> torch.Tensor:
     """Ragged scores [rows_total] fp64: problem p's rows sit at table.row_off[p] : table.row_off[p+1]; columns [j0, j1) of its table entry."""
-    X, N, ldx = _matrix(X)
+    X, N, ldx = fp32_matrix(X, "X")
     out = torch.empty(table.rows_total, dtype=F64, device=X.device)
     check(lib().medp_probe_scores(ptr(X), ldx, N, table.host, ptr(table.dev), ptr(table.rows), table.rows_total, ptr(theta.contiguous()),
                                   ptr(mean.contiguous()), ptr(scale.contiguous()), ptr(out), table.P, table.Fmax, int(bool(intercept)),
@@ -223,7 +214,7 @@ class FittedProbe:
 
     def predict(self, features):
         score = self.decision_function(features)
-        return _expit(score), score
+        return expit(score), score
 
 
 def _feature_tensors(data: Mapping[str, torch.Tensor]):
@@ -375,15 +366,7 @@ def score_parts(data: Mapping[str, torch.Tensor], fits: Sequence[FittedProbe]) -
 # ------------------------------------------------------------------------------------------------------------------------------
 def safe_metrics(y, probability: torch.Tensor) -> Dict[str, float]:
     """`_safe_metrics` (:205-215) through the metrics kernel (one identity replicate); `probability`: a device vector."""
-    m = resampled_binary_metrics(_dev(y, np.uint8, probability.device), probability.to(F64)[None]).cpu().numpy()[0]
-    return {"bce": float(m[0]), "auroc": float(m[1]), "auprc": float(m[2])}
-
-
-def draw_bootstrap_indices(n: int, n_bootstrap: int, seed: int) -> np.ndarray:
-    """The draws of `_bootstrap_differences` (:234-238) -> [n_bootstrap, n] int32."""
-    rng = np.random.default_rng(seed)
-    draws = [rng.integers(0, n, size=n) for _ in range(max(int(n_bootstrap), 0))]
-    return np.stack(draws).astype(np.int32) if draws else np.zeros((0, n), np.int32)
+    return binary_metrics(y, probability)
 
 
 def bootstrap_differences(y, base_probability, probe_probability, n_bootstrap: int, seed: int, device=None, index=None) -> Dict[str, float]:
@@ -397,20 +380,8 @@ def bootstrap_differences(y, base_probability, probe_probability, n_bootstrap: i
     if n > METRICS_MAX_LEN:
         raise ValueError(f"bootstrap_differences: {n} rows exceed METRICS_MAX_LEN = {METRICS_MAX_LEN}")
     index = draw_bootstrap_indices(n, n_bootstrap, seed) if index is None else np.asarray(index, dtype=np.int32).reshape(-1, n)
-    samples = {"bce_gain": np.zeros(0), "auroc_gain": np.zeros(0), "auprc_gain": np.zeros(0)}
-    if len(index):
-        yd = _dev(y, np.uint8, device)
-        idx_d = torch.as_tensor(index.reshape(-1), device=device)
-        off_d = torch.arange(0, (len(index) + 1) * n, n, dtype=torch.int64, device=device)
-        base, probe = (resampled_binary_metrics(yd, _dev(p, np.float64, device)[None], idx_d, off_d, n).cpu().numpy()
-                       for p in (base_probability, probe_probability))
-        both = ~np.isnan(base[:, 1])
-        samples = {"bce_gain": base[:, 0] - probe[:, 0], "auroc_gain": (probe[:, 1] - base[:, 1])[both],
-                   "auprc_gain": (probe[:, 2] - base[:, 2])[both]}
-    output: Dict[str, float] = {}
-    for name, values in samples.items():
-        output[f"{name}_ci_low"], output[f"{name}_ci_high"] = _ci(values)
-    return output
+    offsets = torch.arange(0, (len(index) + 1) * n, n, dtype=torch.int64, device=device)
+    return paired_bootstrap_gains(y, base_probability, probe_probability, index.reshape(-1), offsets, n, device)
 
 
 def permuted_probabilities(model: FittedProbe, parts: Mapping[str, torch.Tensor], image_logit: torch.Tensor, ts_logit: torch.Tensor,
@@ -432,19 +403,9 @@ def conditional_permutation(model: FittedProbe, parts, y, image_logit: torch.Ten
     """Shuffle TS within image-risk bins and summarise the resulting metrics (`_conditional_permutation` :311-351): the reference's
     bins and draws; all `repeats` probability vectors are built on the device and scored by one launch of the metrics kernel."""
     if shuffles is None:
-        bins = image_risk_bins(image_logit.cpu().numpy(), n_bins)
-        rng = np.random.default_rng(seed)
-        shuffles = [conditional_shuffle_indices(bins, rng) for _ in range(max(int(repeats), 0))]
-    samples = np.zeros((0, 3))
-    if len(shuffles):
-        prob = permuted_probabilities(model, parts, image_logit, ts_logit, np.stack(shuffles))
-        samples = resampled_binary_metrics(_dev(y, np.uint8, prob.device), prob).cpu().numpy()
-    output: Dict[str, float] = {}
-    for k, name in enumerate(("bce", "auroc", "auprc")):
-        finite = samples[:, k][np.isfinite(samples[:, k])]
-        output[f"perm_{name}_mean"] = float(finite.mean()) if finite.size else float("nan")
-        output[f"perm_{name}_low"], output[f"perm_{name}_high"] = _ci(finite)
-    return output
+        shuffles = draw_conditional_shuffles(image_logit.cpu().numpy(), n_bins, repeats, seed)
+    prob = permuted_probabilities(model, parts, image_logit, ts_logit, np.stack(shuffles)) if len(shuffles) else None
+    return permutation_summary(y, prob)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -508,34 +469,22 @@ def run_probe(train_data: Mapping[str, torch.Tensor], test_data: Mapping[str, to
             probability_d = torch.sigmoid(part["score"])
             probability, score = probability_d.cpu().numpy(), part["score"].cpu().numpy()
             metrics = safe_metrics(y_test, probability_d)
-            gains = {"bce_gain": base_metrics["bce"] - metrics["bce"], "auroc_gain": metrics["auroc"] - base_metrics["auroc"],
-                     "auprc_gain": metrics["auprc"] - base_metrics["auprc"]}
             confidence = bootstrap_differences(y_test, base_probability, probability, bootstrap, seed + 1000 * k + probe_offset,
                                                probability_d.device)
-            corr_residual = _pearson(score - base_score, y_test.astype(np.float64) - base_probability)
+            corr_residual = pearson(score - base_score, y_test.astype(np.float64) - base_probability)
             permutation = conditional_permutation(model, part, y_test, image_test, ts_test, perm_repeats, perm_bins,
                                                   seed + 10000 * k + probe_offset)
-            perm_bce_increase = permutation["perm_bce_mean"] - metrics["bce"]
-            perm_auroc_drop = metrics["auroc"] - permutation["perm_auroc_mean"]
-            if gains["bce_gain"] > 0 and confidence["bce_gain_ci_low"] > 0 and perm_bce_increase > 0:
-                evidence = "supported"
-            elif gains["bce_gain"] > 0:
-                evidence = "suggestive"
-            else:
-                evidence = "not_detected"
+            fields, evidence = inference_fields(base_metrics, metrics, confidence, corr_residual, permutation)
             row = {"label": label, "probe": probe_name, "n_test": int(len(y_test)), "n_positive": int(y_test.sum()),
-                   "prevalence": float(y_test.mean()), "image_cal_bce": base_metrics["bce"], "image_cal_auroc": base_metrics["auroc"],
-                   "image_cal_auprc": base_metrics["auprc"], "probe_bce": metrics["bce"], "probe_auroc": metrics["auroc"],
-                   "probe_auprc": metrics["auprc"], **gains, **confidence, "corr_residual": corr_residual, **permutation,
-                   "perm_bce_increase": perm_bce_increase, "perm_auroc_drop": perm_auroc_drop, "evidence": evidence}
+                   "prevalence": float(y_test.mean()), **fields, "evidence": evidence}
             assert tuple(row) == ROW_KEYS
             rows.append(row)
             label_summary["probes"][probe_name] = row
             archive[f"{_slug(label)}_{probe_name}_probability"] = probability.astype(np.float32)
-            say(f"{probe_name:<20} {metrics['bce']:.5f} {_fmt(gains['bce_gain'], 5, True):>8} "
+            say(f"{probe_name:<20} {metrics['bce']:.5f} {_fmt(row['bce_gain'], 5, True):>8} "
                 f"[{_fmt(confidence['bce_gain_ci_low'], 5, True):>8},{_fmt(confidence['bce_gain_ci_high'], 5, True):>8}] "
-                f"{metrics['auroc']:.4f} {_fmt(gains['auroc_gain'], 4, True):>7} {metrics['auprc']:.4f} "
-                f"{_fmt(gains['auprc_gain'], 4, True):>7} {_fmt(corr_residual, 3, True):>7} {_fmt(perm_bce_increase, 5, True):>10}  {evidence}")
+                f"{metrics['auroc']:.4f} {_fmt(row['auroc_gain'], 4, True):>7} {metrics['auprc']:.4f} "
+                f"{_fmt(row['auprc_gain'], 4, True):>7} {_fmt(corr_residual, 3, True):>7} {_fmt(row['perm_bce_increase'], 5, True):>10}  {evidence}")
         label_summaries[label] = label_summary
     summary = {"labels": label_summaries, "fits": [{"label": pathology_labels[m.label_index], "probe": m.probe, "C": m.C, "n_iter": m.n_iter,
                                                      "max_gradient": m.max_gradient} for m in fits]}

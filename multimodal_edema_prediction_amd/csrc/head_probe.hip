@@ -30,13 +30,8 @@ __host__ __device__ inline bool head_onchip(int F, int L, int w, int bs) {
     return head_g_bytes(L, bs) + 12 * head_nw(F, L, w) <= HEAD_LDS_BUDGET;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // every thread gets the sum; waves are added in wave order
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+__device__ __forceinline__ double block_sum_wave_order_f64(double v, double* red) {
     v = wave_sum_f64(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
@@ -144,7 +139,7 @@ __device__ __forceinline__ void head_epoch(const MedpHeadProblem& pb, float* gs,
         // ---- vc over the whole minibatch, then g = (sigmoid(z) - y) M / vc and the loss sum
         double part = 0.0;
         for (int e = tid; e < bs * L; e += HT_THREADS) part += (double)pb.M[(size_t)pr[e / L] * pb.ldy + e % L];
-        const double vc = block_sum_f64(part, red);                          // its barriers also publish the logits
+        const double vc = block_sum_wave_order_f64(part, red);               // its barriers also publish the logits
         part = 0.0;
         for (int e = tid; e < bs * L; e += HT_THREADS) {
             const int r = e / L, l = e % L;
@@ -155,7 +150,7 @@ __device__ __forceinline__ void head_epoch(const MedpHeadProblem& pb, float* gs,
             const double sg = z >= 0.0 ? 1.0 / (1.0 + ex) : ex / (1.0 + ex);
             gs[r * LP + l] = vc > 0.0 ? (float)((sg - y) * m / vc) : 0.f;   // vc = 0: the reference's loss is logits.sum() * 0
         }
-        const double lsum = block_sum_f64(part, red);                        // publishes g
+        const double lsum = block_sum_wave_order_f64(part, red);             // publishes g
         if (vc > 0.0) {
             run_l += lsum / vc * vc;
             run_v += vc;

@@ -1,6 +1,7 @@
 // Raw-trajectory conditional probe (reference analysis/raw_trajectory_conditional_probe.py; DESIGN.md "Raw-trajectory probe"):
-// the three data-parallel fp64 parts of the reference's default path.  Everything here is fp64, as in the reference; there is no
-// bf16 mode and functional.precision() is not consulted.
+// the two data-parallel fp64 parts of the reference's default path that are this probe's own (the metrics of its replicates come
+// from binary_metrics.hip).  Everything here is fp64, as in the reference; there is no bf16 mode and functional.precision() is not
+// consulted.
 //
 //   raw_summary_kernel          one thread per (window, variable): the 14 statistics of _summarize_one_variable (:329-405) from the
 //                               [B,T,2V] values | counts tensor, with the reference's centred two-pass std and slopes.
@@ -9,8 +10,6 @@
 //                               registers feed X.W; after the residuals expit(s) - y are known the X^T.R half reads the rows
 //                               back from LDS.  The per-workgroup partial gradients / losses are summed by the finish kernel in
 //                               a fixed order (two-stage, no floating-point atomics: bit-stable).
-//   resampled_metrics_kernel    BCE / AUROC / AUPRC of one resampled replicate per workgroup: gather, clip, bitonic sort in LDS,
-//                               then tie-aware (one threshold per distinct score) ROC area and average precision.
 #include "common.h"
 #include "medp_hip.h"
 
@@ -112,12 +111,6 @@ constexpr int VG_THREADS = 512;                   // 8 waves: two per SIMD
 constexpr int VG_WAVES = VG_THREADS / 64;
 constexpr int VG_MAX_ROWS = 32;                   // rows of X per workgroup
 constexpr int VG_LDS_X = 144 * 1024;              // LDS bytes for the row block (of the CU's 160 KiB; the rest holds R and the wave partials)
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // rows per workgroup: as many as fit the LDS budget, at most VG_MAX_ROWS; 0: not even one row fits, the X^T.R half re-reads
 // the row from global memory (it was just read by the same CU: an L2 hit, not a second HBM pass)
@@ -240,138 +233,6 @@ int launch_valgrad_tile(const double* X, long long ldx, const double* y, const d
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// (c) resampled BCE / AUROC / AUPRC
-// ---------------------------------------------------------------------------------------------------------------------
-constexpr int RM_THREADS = 1024;
-constexpr unsigned long long RM_LABEL = 1ull << 63, RM_SCORE = ~RM_LABEL;     // the clipped score is positive: its sign bit carries the label
-
-struct RmScratch {
-    double red[RM_THREADS];
-    int scan[2][RM_THREADS];
-    int total_pos;
-    int bad;
-};
-
-// fixed-tree sum over the workgroup (the same order on every run)
-__device__ double block_sum_f64(double v, double* red, int tid) {
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int s = RM_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
-__global__ __launch_bounds__(RM_THREADS) void resampled_metrics_kernel(const unsigned char* __restrict__ y, const double* __restrict__ p,
-                                                                        const int* __restrict__ idx, const long long* __restrict__ offsets,
-                                                                        double* __restrict__ out, int N, int Rp, int M) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];   // [M], M a power of two >= the replicate's length
-    __shared__ RmScratch sc;
-    const int tid = threadIdx.x, r = blockIdx.x;
-    const long long o0 = idx ? offsets[r] : 0;
-    const long long len = idx ? offsets[r + 1] - o0 : N;
-    double* o = out + (size_t)r * 3;
-    if (len <= 0 || len > M) {              // empty replicate: NaN by definition; over the staged size: refuse (never index past LDS)
-        if (tid < 3) o[tid] = kNaN;
-        return;
-    }
-    const int L = (int)len;
-    if (tid == 0) sc.bad = 0;
-    __syncthreads();
-    const double* pr = p + (Rp == 1 ? 0 : (size_t)r * N);
-    double bce = 0.0;
-    for (int j = tid; j < M; j += RM_THREADS) {
-        unsigned long long key = 0ull;       // padding: below every clipped score
-        if (j < L) {
-            const int src = idx ? idx[o0 + j] : j;
-            if (src < 0 || src >= N) {
-                sc.bad = 1;
-            } else {
-                const double q = fmin(fmax(pr[src], 1e-7), 1.0 - 1e-7);
-                const bool pos = y[src] != 0;
-                bce -= pos ? log(q) : log(1.0 - q);
-                key = (unsigned long long)__double_as_longlong(q) | (pos ? RM_LABEL : 0ull);
-            }
-        }
-        keys[j] = key;
-    }
-    bce = block_sum_f64(bce, sc.red, tid) / (double)L;
-    if (sc.bad) {                            // an index outside [0, N): no metric is defined
-        if (tid < 3) o[tid] = kNaN;
-        return;
-    }
-    // bitonic sort, descending by score
-    for (int k = 2; k <= M; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < M / 2; t += RM_THREADS) {
-                const int a = ((t & ~(j - 1)) << 1) | (t & (j - 1)), b = a | j;
-                const unsigned long long ka = keys[a], kb = keys[b];
-                const bool desc = (a & k) == 0;
-                if (((ka & RM_SCORE) < (kb & RM_SCORE)) == desc) {
-                    keys[a] = kb;
-                    keys[b] = ka;
-                }
-            }
-            __syncthreads();
-        }
-    // thread t owns positions [c0, c1); positives before c0 by an inclusive scan of the per-thread counts
-    const int C = M > RM_THREADS ? M / RM_THREADS : 1;
-    const int c0 = min(tid * C, L), c1 = min(c0 + C, L);
-    int cnt = 0;
-    for (int j = c0; j < c1; ++j) cnt += (int)(keys[j] >> 63);
-    sc.scan[0][tid] = cnt;
-    __syncthreads();
-    int cur = 0;
-    for (int s = 1; s < RM_THREADS; s <<= 1) {
-        sc.scan[cur ^ 1][tid] = sc.scan[cur][tid] + (tid >= s ? sc.scan[cur][tid - s] : 0);
-        cur ^= 1;
-        __syncthreads();
-    }
-    const int* incl = sc.scan[cur];
-    const int tp0 = incl[tid] - cnt;                                     // positives in [0, c0)
-    const int P = incl[RM_THREADS - 1], Nn = L - P;
-    // positives before the tie group that is open at c0 (its first element may lie in an earlier thread's range)
-    int tp_prev = tp0, fp_prev = c0 - tp0;
-    if (c0 < c1 && c0 > 0 && ((keys[c0 - 1] ^ keys[c0]) & RM_SCORE) == 0) {
-        const unsigned long long target = keys[c0] & RM_SCORE;
-        int lo = 0, hi = c0;                                             // first position whose score is <= target (descending order)
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if ((keys[mid] & RM_SCORE) > target) lo = mid + 1; else hi = mid;
-        }
-        const int owner = lo / C;
-        int tp = owner > 0 ? incl[owner - 1] : 0;
-        for (int j = owner * C; j < lo; ++j) tp += (int)(keys[j] >> 63);
-        tp_prev = tp;
-        fp_prev = lo - tp;
-    }
-    // one threshold per distinct score: the group that ENDS at j contributes a trapezoid to the ROC area and a step to AP
-    long long area2 = 0;                                                 // twice the ROC area in (FP, TP) counts: exact
-    double ap = 0.0;
-    int tp = tp0;
-    for (int j = c0; j < c1; ++j) {
-        tp += (int)(keys[j] >> 63);
-        if (j == L - 1 || ((keys[j] ^ keys[j + 1]) & RM_SCORE) != 0) {
-            const int fp = j + 1 - tp;
-            area2 += (long long)(fp - fp_prev) * (long long)(tp + tp_prev);
-            ap += ((double)(tp - tp_prev) / (double)P) * ((double)tp / (double)(j + 1));
-            tp_prev = tp;
-            fp_prev = fp;
-        }
-    }
-    const double area = block_sum_f64((double)area2, sc.red, tid);      // integers below 2^53: exact in any order
-    ap = block_sum_f64(ap, sc.red, tid);
-    if (tid == 0) {
-        const bool both = P > 0 && Nn > 0;
-        o[0] = bce;
-        o[1] = both ? area / (2.0 * (double)P * (double)Nn) : kNaN;
-        o[2] = both ? ap : kNaN;
-    }
-}
-
 }  // namespace
 
 extern "C" int medp_raw_traj_summary(const float* x, double* out, int B, int T, int V, int recent_hours, void* stream) {
@@ -420,26 +281,5 @@ extern "C" int medp_offset_logistic_valgrad(const double* X, long long ldx, cons
     const int gblocks = (int)(((size_t)F * G + FIN_ELEMS - 1) / FIN_ELEMS);
     valgrad_finish_kernel<<<gblocks + 1, 256, 0, st>>>(gpart, lpart, W, l2, obj, grad, n, F, G, nblocks, gblocks);
     MEDP_LAUNCH_CHECK("medp_offset_logistic_valgrad (finish)");
-    return 0;
-}
-
-extern "C" int medp_resampled_binary_metrics(const unsigned char* y, const double* p, const int* idx, const long long* offsets,
-                                             double* out, int N, int Rp, int R, int max_len, void* stream) {
-    MEDP_CHECK_ARG(y && p && out, "resampled_binary_metrics: null argument");
-    MEDP_CHECK_ARG(N >= 1 && R >= 1, "resampled_binary_metrics: bad shape N=%d R=%d", N, R);
-    MEDP_CHECK_ARG(Rp == 1 || Rp == R, "resampled_binary_metrics: Rp=%d is neither 1 nor R=%d", Rp, R);
-    MEDP_CHECK_ARG(idx == nullptr || offsets != nullptr, "resampled_binary_metrics: a gather needs its offsets");
-    if (idx == nullptr) max_len = N;
-    MEDP_CHECK_ARG(max_len >= 0, "resampled_binary_metrics: max_len %d < 0", max_len);
-    MEDP_CHECK_ARG(max_len <= MEDP_RESAMPLED_METRICS_MAX_LEN, "resampled_binary_metrics: replicate length %d exceeds the in-LDS sort limit %d",
-                   max_len, MEDP_RESAMPLED_METRICS_MAX_LEN);
-    int M = 2;
-    while (M < max_len) M <<= 1;
-    MEDP_ONCE_PER_DEVICE({
-        hipFuncSetAttribute((const void*)resampled_metrics_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            MEDP_RESAMPLED_METRICS_MAX_LEN * 8);
-    });
-    resampled_metrics_kernel<<<R, RM_THREADS, (size_t)M * 8, (hipStream_t)stream>>>(y, p, idx, offsets, out, N, Rp, M);
-    MEDP_LAUNCH_CHECK("medp_resampled_binary_metrics");
     return 0;
 }

@@ -13,6 +13,7 @@ import torch
 
 from . import dp
 from .engine import _move_lists
+from .probe_stats import pearson
 
 
 def auroc(y, score) -> float:
@@ -54,13 +55,7 @@ def _bce_per_sample(logits: np.ndarray, y: np.ndarray) -> np.ndarray:
     return np.maximum(logits, 0) - logits * y + np.log1p(np.exp(-np.abs(logits)))
 
 
-def _pearson(a: np.ndarray, b: np.ndarray) -> float:
-    """evaluator.py:186-194."""
-    if a.size < 2:
-        return float("nan")
-    if a.std() == 0 or b.std() == 0:
-        return float("nan")
-    return float(np.corrcoef(a, b)[0, 1])
+_pearson = pearson        # evaluator.py:186-194: the reference's name for it
 
 
 @torch.no_grad()

@@ -2,7 +2,7 @@
 `unimodal_linear_probe.train_linear_head` and `logit_fusion_probe.train_fusion_head` (DESIGN.md "Linear-head probes").
 
 One `medp_head_train_epoch` launch runs every sequential step of an epoch for P independent heads (one workgroup each); the
-per-epoch selection on validation macro AUROC stays on the device (`medp_head_scores`, `medp_resampled_binary_metrics`, a few
+per-epoch selection on validation macro AUROC stays on the device (`medp_head_scores`, `probe_stats.LabelMetrics`, a few
 elementwise torch ops), so a run of E epochs has no device->host copy and no synchronisation until its single copy at the end.
 
 What runs where
@@ -16,14 +16,13 @@ What runs where
 fusion head): the same selection rule, NOT accelerated.  Without a GPU every entry point raises (no CPU fallback)."""
 from __future__ import annotations
 
-import ctypes
 from typing import Callable, Sequence
 
 import numpy as np
 import torch
 
-from .abi import MedpHeadProblem, check, lib, ptr, require_gpu, stream
-from .raw_trajectory_probe import METRICS_MAX_LEN, resampled_binary_metrics
+from .abi import MedpHeadProblem, check, fp32_matrix, lib, ptr, require_gpu, stream, table_bytes
+from .probe_stats import LabelMetrics, nan_mean
 
 MAX_F, MAX_L, MAX_BS = 32768, 16, 1024          # MEDP_HEAD_MAX_*
 BETAS, EPS = (0.9, 0.999), 1e-8                 # torch.optim.AdamW's defaults, which the reference takes
@@ -48,13 +47,6 @@ def draw_epoch_permutations(n: int, epochs: int) -> np.ndarray:
 # ------------------------------------------------------------------------------------------------------------------------------
 # kernels
 # ------------------------------------------------------------------------------------------------------------------------------
-def _matrix(X: torch.Tensor, what: str):
-    if X.dtype != torch.float32:
-        raise TypeError(f"{what}: the head kernels read fp32")
-    X = X.contiguous()
-    return X, X.shape[0], X.numel() // max(X.shape[0], 1)
-
-
 def onchip(F: int, L: int, label_width: int, bs: int) -> bool:
     """True when W and both Adam moments of such a problem live in LDS for the epoch."""
     return bool(lib().medp_head_train_onchip(int(F), int(L), int(label_width), int(bs)))
@@ -66,9 +58,9 @@ class HeadProblem:
 
     def __init__(self, X, Y, M, W, b, *, col0: int = 0, F: int | None = None, label_width: int = 0, bs: int = 128, lr: float = 1e-4,
                  weight_decay: float = 1e-4, dropout: float = 0.0, seed: int = 0, stream_id: int = 0, betas=BETAS, eps: float = EPS):
-        self.X, self.N, self.ldx = _matrix(X, "X")
-        self.Y, ny, self.ldy = _matrix(Y, "Y")
-        self.M, nm, ldm = _matrix(M, "M")
+        self.X, self.N, self.ldx = fp32_matrix(X, "X")
+        self.Y, ny, self.ldy = fp32_matrix(Y, "Y")
+        self.M, nm, ldm = fp32_matrix(M, "M")
         if ny != self.N or nm != self.N or ldm != self.ldy:
             raise ValueError(f"HeadProblem: X has {self.N} rows, Y {ny} x {self.ldy}, M {nm} x {ldm}")
         dev = self.X.device
@@ -98,8 +90,7 @@ class HeadProblem:
 def make_table(entries: Sequence[MedpHeadProblem]):
     """(host ctypes array, the same bytes as a uint8 numpy array)."""
     host = (MedpHeadProblem * max(len(entries), 1))(*entries)
-    raw = np.frombuffer(host, dtype=np.uint8, count=ctypes.sizeof(MedpHeadProblem) * len(entries)).copy()
-    return host, raw
+    return host, table_bytes(host, len(entries))
 
 
 def check_table(entries: Sequence[MedpHeadProblem]) -> None:
@@ -129,7 +120,7 @@ def head_scores(X, W, b, *, col0: int = 0, F: int | None = None, label_width: in
                 probs=None):
     """(logits [n, L] fp32, probs [L, n] fp64 = the fp32 sigmoid widened) of the rows `rows` (int32, device; None: all rows)."""
     require_gpu()
-    X, N, ldx = _matrix(X, "X")
+    X, N, ldx = fp32_matrix(X, "X")
     L = int(b.numel())
     F = ldx - col0 if F is None else F
     n = N if rows is None else int(rows.numel())
@@ -145,40 +136,6 @@ def head_scores(X, W, b, *, col0: int = 0, F: int | None = None, label_width: in
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# per-label metrics of a split
-# ------------------------------------------------------------------------------------------------------------------------------
-class LabelMetrics:
-    """AUROC / AUPRC / BCE of every label over its known rows, in ONE `medp_resampled_binary_metrics` launch: y and p are flattened
-    to [L n] (label-major) and replicate l is the index list of label l's known rows, offset by l n."""
-
-    def __init__(self, Y: torch.Tensor, M: torch.Tensor):
-        dev = Y.device
-        self.n, self.L = Y.shape
-        known = M.detach().to("cpu").numpy().astype(bool)                              # once, before the first launch
-        self.counts = known.sum(0)
-        if self.counts.max(initial=0) > METRICS_MAX_LEN:
-            raise ValueError(f"a label has {int(self.counts.max())} known rows: more than the metrics kernel's "
-                             f"MEDP_RESAMPLED_METRICS_MAX_LEN = {METRICS_MAX_LEN}")
-        idx = [np.flatnonzero(known[:, l]).astype(np.int32) + l * self.n for l in range(self.L)]
-        self.idx = torch.as_tensor(np.concatenate(idx) if idx else np.zeros(0, np.int32), device=dev)
-        self.offsets = torch.as_tensor(np.concatenate(([0], np.cumsum(self.counts))).astype(np.int64), device=dev)
-        self.y = (Y.detach().t() > 0.5).to(torch.uint8).contiguous().reshape(-1)
-        self.max_len = max(int(self.counts.max(initial=0)), 1)
-        if self.idx.numel() == 0:                                                      # nothing known at all: a valid (empty) index list
-            self.idx = torch.zeros(1, dtype=torch.int32, device=dev)
-
-    def __call__(self, probs: torch.Tensor) -> torch.Tensor:
-        """probs [L, n] fp64 -> [L, 3] fp64 = BCE, AUROC, AUPRC per label (NaN: fewer than two known rows, or one class)."""
-        return resampled_binary_metrics(self.y, probs.reshape(1, -1), self.idx, self.offsets, self.max_len)
-
-
-def nan_mean(v: torch.Tensor) -> torch.Tensor:
-    """Mean of the entries that are not NaN; NaN when there is none (a device scalar, no synchronisation)."""
-    ok = ~torch.isnan(v)
-    return torch.where(ok, v, torch.zeros_like(v)).sum() / ok.sum()
-
-
-# ------------------------------------------------------------------------------------------------------------------------------
 # the trainer
 # ------------------------------------------------------------------------------------------------------------------------------
 def train_heads(problems: Sequence[HeadProblem], vals: Sequence[tuple], epochs: int, perms: Sequence[np.ndarray],
@@ -191,7 +148,7 @@ def train_heads(problems: Sequence[HeadProblem], vals: Sequence[tuple], epochs: 
     P, E = len(problems), int(epochs)
     dev = problems[0].X.device
     metrics = [LabelMetrics(v[1].to(dev), v[2].to(dev)) for v in vals]                 # raises before the first launch
-    Xv = [_matrix(v[0].to(dev), "X_va")[0] for v in vals]
+    Xv = [fp32_matrix(v[0].to(dev), "X_va")[0] for v in vals]
     perm_dev = [torch.as_tensor(np.ascontiguousarray(np.asarray(pm)[:, :pb.S * pb.bs], dtype=np.int32), device=dev)
                 for pb, pm in zip(problems, perms)]
     for pb, pd in zip(problems, perm_dev):

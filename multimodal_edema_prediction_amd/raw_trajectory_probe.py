@@ -3,12 +3,13 @@ model on the `level`, `trajectory`, `observation`, `physiologic` and `all` block
 
 The reference's names without the leading underscore and its return shapes, so that the body of its `main()` label / block loop
 (:927-1075) restates on top of this module; `run_probe` is that restatement for one label.  All arithmetic is fp64, as in the
-reference: there is no bf16 mode and `functional.precision()` is not consulted.
+reference: there is no bf16 mode and `functional.precision()` is not consulted.  The resampling functions that carry the reference's
+names are this probe's own draw or probability construction followed by a call into probe_stats.py, which all analysis probes share.
 
 What runs where
   device, HIP   `raw_traj_summary` (the 14 statistics per (window, variable)), `offset_logistic_valgrad` (objective + gradient of G
-                candidates per launch; also the held-out BCE of a fold), `resampled_binary_metrics` (BCE / AUROC / AUPRC of every
-                bootstrap or permutation replicate in one launch).
+                candidates per launch; also the held-out BCE of a fold), `probe_stats.resampled_binary_metrics` (csrc/binary_metrics.hip:
+                BCE / AUROC / AUPRC of every bootstrap or permutation replicate in one launch).
   device, torch median imputation + missing indicators + standardisation (fp64), the batched L-BFGS two-loop recursion and its
                 masked line search (no host round trip but ONE convergence flag per evaluation), the final X.w of a prediction.
   host, numpy   the index draws (`default_rng(seed)`, the reference's call order, so the replicates ARE the reference's), the fold
@@ -24,6 +25,8 @@ import numpy as np
 import torch
 
 from .abi import check, lib, ptr, stream
+from .probe_stats import (binary_metrics, draw_cluster_bootstrap_indices, draw_conditional_shuffles, expit, inference_fields,
+                          paired_bootstrap_gains, pearson, permutation_summary, to_device, to_host, unit_or_sd)
 
 F64 = torch.float64
 LEVEL_STATS = ("last", "mean", "std", "min", "max")
@@ -33,7 +36,6 @@ DEFAULT_BLOCKS = ("level", "trajectory", "observation", "physiologic", "all")
 DEFAULT_L2_GRID = (0.0001, 0.001, 0.01, 0.1, 1.0, 10.0, 100.0)
 DEFAULT_C_GRID = (0.001, 0.01, 0.1, 1.0, 10.0)
 MAX_CANDIDATES = 8             # MEDP_OFFSET_LOGISTIC_MAX_G
-METRICS_MAX_LEN = 16384        # MEDP_RESAMPLED_METRICS_MAX_LEN: the longest replicate one workgroup sorts in LDS
 GTOL = 1e-7                    # the reference's L-BFGS-B `gtol` (max-norm of the gradient)
 
 
@@ -76,25 +78,6 @@ def valgrad_workspace(n: int, F: int, G: int, device) -> torch.Tensor:
     if nbytes == 0:
         raise ValueError(f"offset_logistic_valgrad: bad shape n={n} F={F} G={G} (1 <= G <= {MAX_CANDIDATES})")
     return torch.empty(nbytes // 8, dtype=F64, device=device)
-
-
-def resampled_binary_metrics(y, p, idx=None, offsets=None, max_len=None) -> torch.Tensor:
-    """y [N] u8, p [Rp,N] fp64, idx int32 / offsets int64 [R+1] (device) -> [R,3] fp64 = BCE, AUROC, AUPRC per replicate.
-    idx None: R = Rp identity replicates.  `max_len`: the longest replicate (known to the caller, who drew the indices)."""
-    Rp, N = p.shape
-    if idx is None:
-        R, max_len = Rp, N
-    else:
-        R = offsets.numel() - 1
-        if max_len is None:
-            max_len = int((offsets[1:] - offsets[:-1]).max())
-    if y.dtype != torch.uint8 or p.dtype != F64 or (idx is not None and (idx.dtype != torch.int32 or offsets.dtype != torch.int64)):
-        raise TypeError("resampled_binary_metrics: y u8, p fp64, idx int32, offsets int64")
-    y, p = y.contiguous(), p.contiguous()
-    out = torch.empty((R, 3), dtype=F64, device=p.device)
-    check(lib().medp_resampled_binary_metrics(ptr(y), ptr(p), ptr(idx), ptr(offsets), ptr(out), N, Rp, R, int(max_len), stream()),
-          "resampled_binary_metrics")
-    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -177,9 +160,7 @@ class Preprocessor:
         n = Z.shape[0]
         mean = Z.mean(0)
         var = ((Z - mean) ** 2).mean(0)                                   # population variance
-        eps = torch.finfo(F64).eps                                        # sklearn's constant-column test: such a column keeps scale 1
-        constant = var <= n * eps * var + (n * mean * eps) ** 2
-        pre.mean, pre.scale = mean, torch.where(constant, torch.ones_like(var), var.sqrt())
+        pre.mean, pre.scale = mean, unit_or_sd(var, mean, n)              # a constant column keeps scale 1
         return pre
 
     def _impute(self, X):
@@ -299,7 +280,7 @@ class OffsetCorrectionModel:
 
     def predict(self, fixed_image_score, raw_features: torch.Tensor):
         score = self.decision_function(fixed_image_score, raw_features)
-        return _expit(score), score
+        return expit(score), score
 
     def standardized_coefficients(self):
         return sorted([(name, float(c)) for name, c in zip(self.transformed_names, self.weights)], key=lambda item: abs(item[1]),
@@ -315,9 +296,9 @@ def fit_offset_correction(raw_train, y_train, fixed_image_score, l2_grid: Sequen
         raise ValueError("null_tolerance must be non-negative")
     dev = raw_train.device
     raw_train = raw_train.to(F64)
-    y_host = _host(y_train).astype(np.int64)
+    y_host = to_host(y_train).astype(np.int64)
     folds = stratified_folds(y_host, cv_folds, seed) if folds is None else _check_folds(y_host, folds, cv_folds)
-    y, offset = _dev(y_host, np.float64, dev), _dev(_host(fixed_image_score), np.float64, dev)
+    y, offset = to_device(y_host, np.float64, dev), to_device(fixed_image_score, np.float64, dev)
     input_names = tuple(f"x{i}" for i in range(raw_train.shape[1])) if input_names is None else tuple(str(n) for n in input_names)
     candidate_names = ["null"] + [f"l2={value:g}" for value in l2_grid]
     zeros = torch.zeros(len(l2_grid), dtype=F64, device=dev)
@@ -353,86 +334,17 @@ def _chunked_objective(X, y, offset, W, l2):
                       for i in range(0, W.shape[1], MAX_CANDIDATES)])
 
 
-def _dev(a, dtype, device) -> torch.Tensor:
-    """A host vector, copied (read-only inputs stay untouched) and converted, on the device."""
-    return torch.as_tensor(np.array(_host(a), dtype=dtype), device=device)
-
-
-def _host(a) -> np.ndarray:
-    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-
-
-def _expit(s: np.ndarray) -> np.ndarray:
-    e = np.exp(-np.abs(s))
-    return np.where(s >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
-
-
 # ------------------------------------------------------------------------------------------------------------------------------
 # resampling
 # ------------------------------------------------------------------------------------------------------------------------------
-def image_risk_bins(image_logit: np.ndarray, n_bins: int) -> np.ndarray:
-    """`_image_risk_bins` (:130-138)."""
-    if n_bins <= 1:
-        return np.zeros(len(image_logit), dtype=np.int64)
-    edges = np.unique(np.quantile(image_logit, np.linspace(0.0, 1.0, int(n_bins) + 1)))
-    if len(edges) <= 2:
-        return np.zeros(len(image_logit), dtype=np.int64)
-    return np.digitize(image_logit, edges[1:-1], right=True).astype(np.int64)
-
-
-def conditional_shuffle_indices(bins: np.ndarray, rng: np.random.Generator) -> np.ndarray:
-    """`_conditional_shuffle_indices` (:141-149): the same draws from `rng`."""
-    shuffled = np.arange(len(bins))
-    for value in np.unique(bins):
-        members = np.flatnonzero(bins == value)
-        if len(members) > 1:
-            shuffled[members] = rng.permutation(members)
-    return shuffled
-
-
-def draw_cluster_bootstrap_indices(subject_ids: np.ndarray, n_bootstrap: int, seed: int):
-    """The patient-cluster draws of `_cluster_bootstrap_differences` (:771-777) -> (idx int32 concatenated, offsets int64 [R+1])."""
-    unique_subjects = np.unique(subject_ids)
-    members = {subject: np.flatnonzero(subject_ids == subject) for subject in unique_subjects}
-    rng = np.random.default_rng(seed)
-    parts = []
-    for _ in range(max(int(n_bootstrap), 0)):
-        drawn = rng.choice(unique_subjects, size=len(unique_subjects), replace=True)
-        parts.append(np.concatenate([members[subject] for subject in drawn]))
-    offsets = np.cumsum([0] + [len(p) for p in parts]).astype(np.int64)
-    idx = np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
-    return idx, offsets
-
-
-def _ci(values: np.ndarray):
-    if values.size:
-        low, high = np.percentile(values, [2.5, 97.5])
-        return float(low), float(high)
-    return float("nan"), float("nan")
-
-
 def cluster_bootstrap_differences(y, base_probability, probe_probability, subject_ids, n_bootstrap: int, seed: int,
                                   device=None) -> Dict[str, float]:
     """Paired patient-cluster bootstrap; positive values favor the probe (`_cluster_bootstrap_differences` :760-801).  The draws are
     the reference's; both probability vectors are scored on every replicate by two launches of the metrics kernel."""
     device = torch.device("cuda") if device is None else device
-    y, subject_ids = np.asarray(y), np.asarray(subject_ids)
-    idx, offsets = draw_cluster_bootstrap_indices(subject_ids, n_bootstrap, seed)
-    samples = {"bce_gain": np.zeros(0), "auroc_gain": np.zeros(0), "auprc_gain": np.zeros(0)}
-    if len(offsets) > 1:
-        yd = _dev(y, np.uint8, device)
-        idx_d, off_d = torch.as_tensor(idx, device=device), torch.as_tensor(offsets, device=device)
-        max_len = int(np.diff(offsets).max())
-        m = [resampled_binary_metrics(yd, _dev(p, np.float64, device)[None], idx_d, off_d, max_len)
-             for p in (base_probability, probe_probability)]
-        base, probe = m[0].cpu().numpy(), m[1].cpu().numpy()
-        both = ~np.isnan(base[:, 1])                                     # replicates with both classes present
-        samples = {"bce_gain": base[:, 0] - probe[:, 0], "auroc_gain": (probe[:, 1] - base[:, 1])[both],
-                   "auprc_gain": (probe[:, 2] - base[:, 2])[both]}
-    output: Dict[str, float] = {}
-    for metric, values in samples.items():
-        output[f"{metric}_ci_low"], output[f"{metric}_ci_high"] = _ci(values)
-    return output
+    idx, offsets = draw_cluster_bootstrap_indices(np.asarray(subject_ids), n_bootstrap, seed)
+    max_len = int(np.diff(offsets).max()) if len(offsets) > 1 else 0
+    return paired_bootstrap_gains(np.asarray(y), base_probability, probe_probability, idx, offsets, max_len, device)
 
 
 def conditional_permutation_offset(model: OffsetCorrectionModel, y, image_logit, fixed_image_score, raw_features: torch.Tensor,
@@ -441,28 +353,17 @@ def conditional_permutation_offset(model: OffsetCorrectionModel, y, image_logit,
     pre-processing is row-wise, so shuffling the rows shuffles the corrections X.w: one gather builds all `repeats` probability
     vectors on the device and one launch of the metrics kernel scores them."""
     dev = raw_features.device
-    bins = image_risk_bins(np.asarray(image_logit), n_bins)
-    rng = np.random.default_rng(seed)
-    shuffles = [conditional_shuffle_indices(bins, rng) for _ in range(max(int(repeats), 0))]
-    samples = np.zeros((0, 3))
-    if shuffles:
-        fixed = _dev(fixed_image_score, np.float64, dev)
-        corr = model.correction(raw_features)
-        prob = torch.sigmoid(fixed[None, :] + corr[torch.as_tensor(np.stack(shuffles), device=dev)])
-        samples = resampled_binary_metrics(_dev(y, np.uint8, dev), prob).cpu().numpy()
-    output: Dict[str, float] = {}
-    for k, metric in enumerate(("bce", "auroc", "auprc")):
-        finite = samples[:, k][np.isfinite(samples[:, k])]
-        output[f"perm_{metric}_mean"] = float(finite.mean()) if finite.size else float("nan")
-        output[f"perm_{metric}_low"], output[f"perm_{metric}_high"] = _ci(finite)
-    return output
+    shuffles = draw_conditional_shuffles(np.asarray(image_logit), n_bins, repeats, seed)
+    if not shuffles:
+        return permutation_summary(y, None)
+    fixed = to_device(fixed_image_score, np.float64, dev)
+    corr = model.correction(raw_features)
+    return permutation_summary(y, torch.sigmoid(fixed[None, :] + corr[torch.as_tensor(np.stack(shuffles), device=dev)]))
 
 
 def safe_metrics(y, probability, device=None) -> Dict[str, float]:
     """`_safe_metrics` (:109-119) through the metrics kernel (one identity replicate)."""
-    device = torch.device("cuda") if device is None else device
-    m = resampled_binary_metrics(_dev(y, np.uint8, device), _dev(probability, np.float64, device)[None]).cpu().numpy()[0]
-    return {"bce": float(m[0]), "auroc": float(m[1]), "auprc": float(m[2])}
+    return binary_metrics(y, probability, device)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -478,7 +379,7 @@ def _newton_logistic(z, y, C, iters=100):
 
     f = value(w, b)
     for _ in range(iters):
-        p = _expit(w * z + b)
+        p = expit(w * z + b)
         r, h = p - y, p * (1.0 - p)
         g = np.array([C * np.sum(r * z) + w, C * np.sum(r)])
         if np.abs(g).max() <= 1e-12 * max(1.0, C * len(y)):
@@ -509,12 +410,12 @@ class ImageCalibration:
 
     def predict(self, image_logit):
         score = self.decision_function(image_logit)
-        return _expit(score), score
+        return expit(score), score
 
 
 def _fit_scaled_logistic(z, y, C):
     mean, var = z.mean(), z.var()
-    scale = np.sqrt(var) if var > len(z) * np.finfo(np.float64).eps * var + (len(z) * mean * np.finfo(np.float64).eps) ** 2 else 1.0
+    scale = unit_or_sd(var, mean, len(z))
     w, b = _newton_logistic((z - mean) / scale, y, C)
     return mean, scale, w, b
 
@@ -543,13 +444,6 @@ def calibrate_image_logit(image_train, y_train, c_grid: Sequence[float] = DEFAUL
 # ------------------------------------------------------------------------------------------------------------------------------
 # the label / block loop
 # ------------------------------------------------------------------------------------------------------------------------------
-def _pearson(a: np.ndarray, b: np.ndarray) -> float:
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    if a.size < 2 or a.std() == 0 or b.std() == 0:
-        return float("nan")
-    return float(np.corrcoef(a, b)[0, 1])
-
-
 def run_probe(train_blocks: Mapping[str, torch.Tensor], test_blocks: Mapping[str, torch.Tensor], block_names: Mapping[str, Sequence[str]],
               y_train, y_test, image_train, image_test, subject_test, *, label: str = "label", label_index: int = 0,
               blocks: Sequence[str] = DEFAULT_BLOCKS, c_grid: Sequence[float] = DEFAULT_C_GRID,
@@ -579,28 +473,15 @@ def run_probe(train_blocks: Mapping[str, torch.Tensor], test_blocks: Mapping[str
                                        folds=None if correction_folds is None else correction_folds.get(block), input_names=names)
         probability, score = fitted.predict(base_score, raw_test)
         metrics = safe_metrics(y_test, probability, dev)
-        gains = {"bce_gain": base_metrics["bce"] - metrics["bce"], "auroc_gain": metrics["auroc"] - base_metrics["auroc"],
-                 "auprc_gain": metrics["auprc"] - base_metrics["auprc"]}
         confidence = cluster_bootstrap_differences(y_test, base_probability, probability, subject_test, bootstrap,
                                                    seed + label_index * 10000 + probe_offset, dev)
-        corr_residual = _pearson(score - base_score, y_test.astype(np.float64) - base_probability)
+        corr_residual = pearson(score - base_score, y_test.astype(np.float64) - base_probability)
         permutation = conditional_permutation_offset(fitted, y_test, image_test, base_score, raw_test, perm_repeats, perm_bins,
                                                      seed + label_index * 100000 + probe_offset)
-        perm_bce_increase = permutation["perm_bce_mean"] - metrics["bce"]
-        perm_auroc_drop = metrics["auroc"] - permutation["perm_auroc_mean"]
-        if gains["bce_gain"] > 0 and confidence["bce_gain_ci_low"] > 0 and perm_bce_increase > 0:
-            evidence = "supported"
-        elif gains["bce_gain"] > 0:
-            evidence = "suggestive"
-        else:
-            evidence = "not_detected"
+        fields, evidence = inference_fields(base_metrics, metrics, confidence, corr_residual, permutation)
         rows.append({
             "label": label, "model": "offset_logistic", "block": block, "n_test": int(len(y_test)), "n_positive": int(y_test.sum()),
-            "prevalence": float(y_test.mean()), "n_input_features": int(raw_train.shape[1]),
-            "image_cal_bce": base_metrics["bce"], "image_cal_auroc": base_metrics["auroc"], "image_cal_auprc": base_metrics["auprc"],
-            "probe_bce": metrics["bce"], "probe_auroc": metrics["auroc"], "probe_auprc": metrics["auprc"],
-            **gains, **confidence, "corr_residual": corr_residual, **permutation,
-            "perm_bce_increase": perm_bce_increase, "perm_auroc_drop": perm_auroc_drop, "inner_cv_bce": fitted.cv_bce,
+            "prevalence": float(y_test.mean()), "n_input_features": int(raw_train.shape[1]), **fields, "inner_cv_bce": fitted.cv_bce,
             "best_params": json.dumps(fitted.best_params_, sort_keys=True),
             "correction_cv_results": json.dumps(fitted.cv_results, sort_keys=True),
             "null_selected": fitted.null_selected, "evidence": evidence})

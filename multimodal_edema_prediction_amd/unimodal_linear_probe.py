@@ -28,7 +28,7 @@ from .abi import require_gpu
 from .cohort import PATHOLOGY_LABELS, CohortCfg, SyntheticCohort, collate
 from .cxr import CXREncoder
 from .duett import load_duett_backbone
-from .raw_trajectory_probe import METRICS_MAX_LEN
+from .probe_stats import METRICS_MAX_LEN, LabelMetrics
 
 DEFAULTS = {"duett_ckpt": "synthetic", "cxr_model_name": "synthetic"}
 FEATURE_TYPES = ("rep", "hourly_mean", "multiscale", "attn_pool")
@@ -147,7 +147,7 @@ def _table_from_logits(logits: torch.Tensor, Y, M, label_names: Sequence[str], p
     y_h = Y.cpu().numpy()
     n_known = known.sum(0)
     if z.is_cuda and n_known.max(initial=0) <= METRICS_MAX_LEN:
-        m = head_probe.LabelMetrics(Y.to(z.device), M.to(z.device))(probs.t().contiguous().double()).cpu().numpy()
+        m = LabelMetrics(Y.to(z.device), M.to(z.device))(probs.t().contiguous().double()).cpu().numpy()
         au, pr = m[:, 1], m[:, 2]
     else:
         p_h = probs.cpu().numpy()

@@ -1,5 +1,5 @@
-"""Numpy restatement of the three raw-trajectory-probe kernels (csrc/raw_probe.hip), pinned on tests/golden/raw_probe.npz by
-tests/test_raw_probe_refs_cpu.py and compared with the kernels by tests/test_gpu_raw_probe_kernels.py.  Written from the reference's
+"""Numpy restatement of the three raw-trajectory-probe kernels (csrc/raw_probe.hip, csrc/binary_metrics.hip), pinned on
+tests/golden/raw_probe.npz by tests/test_raw_probe_refs_cpu.py and compared with the kernels by tests/test_gpu_raw_probe_kernels.py.  Written from the reference's
 definitions (analysis/raw_trajectory_conditional_probe.py), not from the kernels: the summaries walk the hours in order with the
 reference's centred two-pass formulas, AUROC is the Mann-Whitney statistic on tie-averaged ranks and AUPRC the step sum over distinct
 thresholds."""

@@ -85,15 +85,15 @@ def test_scores_restatement_gives_the_reference_scores():
 
 
 def test_index_draws_are_the_references():
-    g, cip = golden(), _cip()
+    from multimodal_edema_prediction_amd.probe_stats import conditional_shuffle_indices, draw_bootstrap_indices, image_risk_bins
+    g = golden()
     cfg = g["cfg"]
     seed, n_boot, n_perm, bins_n = int(cfg[5]), int(cfg[6]), int(cfg[7]), int(cfg[8])
     img, _, _, y = _label(g, "test", 0)
     probe_offset = PROBE_NAMES.index("token_linear")
-    idx = cip.draw_bootstrap_indices(len(y), n_boot, seed + probe_offset)
+    idx = draw_bootstrap_indices(len(y), n_boot, seed + probe_offset)
     assert idx.dtype == np.int32 and np.array_equal(idx, g["boot_idx"]) and np.array_equal(idx, draw_bootstrap_ref(len(y), n_boot, seed + probe_offset))
-    assert cip.draw_bootstrap_indices(len(y), 0, 1).shape == (0, len(y))
-    from multimodal_edema_prediction_amd.raw_trajectory_probe import conditional_shuffle_indices, image_risk_bins
+    assert draw_bootstrap_indices(len(y), 0, 1).shape == (0, len(y))
     bins = image_risk_bins(img, bins_n)
     assert np.array_equal(bins, g["perm_bins"])
     rng = np.random.default_rng(seed + probe_offset)

@@ -118,7 +118,7 @@ def test_run_probe_against_the_reference_as_shipped():
 
 def test_per_replicate_metrics_equal_the_references():
     g, cip = golden(), _cip()
-    from multimodal_edema_prediction_amd.raw_trajectory_probe import resampled_binary_metrics
+    from multimodal_edema_prediction_amd.probe_stats import resampled_binary_metrics
     d = lambda a: torch.as_tensor(np.array(a), device=DEV)  # noqa: E731
     y_test = g["test_y"][_known("test", 0), 0].astype(np.uint8)
     n, idx = len(y_test), g["boot_idx"].astype(np.int32)

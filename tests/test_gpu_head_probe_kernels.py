@@ -10,7 +10,7 @@ import torch
 
 import dropout_twin
 import head_probe_refs as refs
-from multimodal_edema_prediction_amd import evaluator, head_probe
+from multimodal_edema_prediction_amd import evaluator, head_probe, probe_stats
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -231,12 +231,12 @@ def test_device_metrics_equal_the_host_evaluator_on_the_same_probabilities(score
     Y, M = np.nan_to_num(c["Y"][rows, :7]), np.nan_to_num(c["M"][rows, :7])
     M[:, 5] = 0.0                                                           # a label without a known row: NaN, skipped by the macro mean
     Y[:, 6] = 1.0                                                           # one class only: NaN too
-    m = head_probe.LabelMetrics(torch.as_tensor(Y, device=DEV), torch.as_tensor(M, device=DEV))(probs).cpu().numpy()
+    m = probe_stats.LabelMetrics(torch.as_tensor(Y, device=DEV), torch.as_tensor(M, device=DEV))(probs).cpu().numpy()
     p = probs.cpu().numpy()
     for l in range(5):
         k = M[:, l] > 0.5
         assert abs(m[l, 1] - evaluator.auroc(Y[k, l], p[l, k])) <= 1e-12 and abs(m[l, 2] - evaluator.average_precision(Y[k, l], p[l, k])) <= 1e-12
     assert np.isnan(m[5, 1]) and np.isnan(m[6, 1])
-    macro = float(head_probe.nan_mean(torch.as_tensor(m[:, 1], device=DEV)).item())
+    macro = float(probe_stats.nan_mean(torch.as_tensor(m[:, 1], device=DEV)).item())
     assert abs(macro - np.mean(m[:5, 1])) <= 1e-15
     assert abs(macro - refs.macro_auroc(logits.cpu().numpy(), Y, M)) <= 1e-12

@@ -28,6 +28,11 @@ def _rp():
     return raw_trajectory_probe
 
 
+def _ps():
+    from multimodal_edema_prediction_amd import probe_stats
+    return probe_stats
+
+
 def _blocks():
     """Summaries of both splits on the device, once; the noise block rides along."""
     if "blocks" not in _state:
@@ -128,7 +133,7 @@ def test_a_pure_noise_block_selects_the_null_candidate():
     assert margin >= float(g["null_tolerance"])                          # as far from the decision boundary as the reference is
     _, test, _ = _blocks()
     prob, _ = model.predict(g["cal_test_score"], test["noise"])
-    assert np.array_equal(prob, _rp()._expit(g["cal_test_score"]))       # the exact null: the calibrated image predictor, untouched
+    assert np.array_equal(prob, _ps().expit(g["cal_test_score"]))       # the exact null: the calibrated image predictor, untouched
 
 
 def test_the_metrics_kernel_reproduces_the_reference_on_every_replicate():
@@ -139,7 +144,7 @@ def test_the_metrics_kernel_reproduces_the_reference_on_every_replicate():
     y = d(g["y_test"].astype(np.uint8))
     idx, offsets = d(g["boot_idx"].astype(np.int32)), d(g["boot_offsets"].astype(np.int64))
     for p, want in ((g["cal_test_prob"], g["boot_metrics_base"]), (g["level_test_prob"], g["boot_metrics_probe"])):
-        got = rp.resampled_binary_metrics(y, d(p[None]), idx, offsets).cpu().numpy()
+        got = _ps().resampled_binary_metrics(y, d(p[None]), idx, offsets).cpu().numpy()
         np.testing.assert_allclose(got, want, rtol=1e-10, atol=1e-10)
     assert rp.safe_metrics(g["y_test"], g["level_test_prob"]) == pytest.approx(dict(zip(("bce", "auroc", "auprc"), g["level_metrics"])), abs=1e-10)
 

@@ -1,5 +1,6 @@
-"""GPU: the three kernels of csrc/raw_probe.hip against their numpy restatement (tests/raw_probe_refs.py, itself pinned on the
-reference's outputs by tests/test_raw_probe_refs_cpu.py).
+"""GPU: the two kernels of csrc/raw_probe.hip and the metrics kernel of csrc/binary_metrics.hip against their numpy restatement
+(tests/raw_probe_refs.py, itself pinned on the reference's outputs by tests/test_raw_probe_refs_cpu.py), and the shared resampling
+of probe_stats.py on top of the metrics kernel.
 
 Tolerances (fp64 everywhere; kernel and restatement differ in summation order and in libm's exp / log / log1p by an ulp or two):
   summaries  sums of T <= 96 terms of magnitude <= ~1e3 (count * value): 96 * 1.1e-16 * 1e3 ~ 1e-11 absolute, amplified by the
@@ -14,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from raw_probe_refs import (EXACT_STATS, METRICS_MAX_LEN, STATS, offset_logistic_valgrad_ref, raw_traj_summary_ref,
+from raw_probe_refs import (EXACT_STATS, METRICS_MAX_LEN, STATS, binary_metrics_ref, offset_logistic_valgrad_ref, raw_traj_summary_ref,
                             resampled_binary_metrics_ref)
 
 pytestmark = pytest.mark.gpu
@@ -24,6 +25,11 @@ DEV = "cuda"
 def _rp():
     from multimodal_edema_prediction_amd import raw_trajectory_probe
     return raw_trajectory_probe
+
+
+def _ps():
+    from multimodal_edema_prediction_amd import probe_stats
+    return probe_stats
 
 
 def _abi():
@@ -146,14 +152,14 @@ def test_resampled_binary_metrics_with_a_ragged_gather(quantised, per_replicate_
     P = np.stack([np.roll(p, r) for r in range(R)]) if per_replicate_p else p[None]
     want = resampled_binary_metrics_ref(y, P, idx, offsets)
     d = lambda a: torch.as_tensor(a, device=DEV)  # noqa: E731
-    got = _rp().resampled_binary_metrics(d(y), d(P), d(idx), d(offsets), max_len=max(LENGTHS)).cpu().numpy()
+    got = _ps().resampled_binary_metrics(d(y), d(P), d(idx), d(offsets), max_len=max(LENGTHS)).cpu().numpy()
     assert np.array_equal(np.isnan(got), np.isnan(want))
     np.testing.assert_allclose(got, want, rtol=1e-10, atol=1e-10, equal_nan=True)
     assert np.isnan(got[LENGTHS.index(0)]).all()                         # the empty replicate: NaN, NaN, NaN by definition
     for r in (R - 2, R - 1):                                             # one class only: AUROC / AUPRC NaN, BCE finite
         assert np.isfinite(got[r, 0]) and np.isnan(got[r, 1:]).all()
     assert np.isnan(got[0, 1]) and np.isfinite(got[0, 0])                # length 1 is one class too
-    again = _rp().resampled_binary_metrics(d(y), d(P), d(idx), d(offsets), max_len=max(LENGTHS))
+    again = _ps().resampled_binary_metrics(d(y), d(P), d(idx), d(offsets), max_len=max(LENGTHS))
     assert np.array_equal(again.cpu().numpy(), got, equal_nan=True)
 
 
@@ -164,12 +170,12 @@ def test_resampled_binary_metrics_identity(N, Rp):
     y[:2] = (0, 1)
     P = np.round(rng.random((Rp, N)), 1)                                 # ties
     want = resampled_binary_metrics_ref(y, P)
-    got = _rp().resampled_binary_metrics(torch.as_tensor(y, device=DEV), torch.as_tensor(P, device=DEV)).cpu().numpy()
+    got = _ps().resampled_binary_metrics(torch.as_tensor(y, device=DEV), torch.as_tensor(P, device=DEV)).cpu().numpy()
     np.testing.assert_allclose(got, want, rtol=1e-10, atol=1e-10)
 
 
 def test_resampled_binary_metrics_limit_and_bad_index():
-    abi, rp = _abi(), _rp()
+    abi, rp = _abi(), _ps()
     N = 50
     y = torch.zeros(N, dtype=torch.uint8, device=DEV)
     y[::2] = 1
@@ -193,3 +199,83 @@ def test_resampled_binary_metrics_limit_and_bad_index():
     # a replicate longer than the max_len the caller declared is refused on the device, not sorted past the staged size
     got = rp.resampled_binary_metrics(y, p, idx, offsets, max_len=2).cpu().numpy()
     assert np.isnan(got).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+CI_KEYS = [f"{m}_gain_ci_{side}" for m in ("bce", "auroc", "auprc") for side in ("low", "high")]
+PERM_KEYS = [f"perm_{m}_{s}" for m in ("bce", "auroc", "auprc") for s in ("mean", "low", "high")]
+
+
+def _stats_case():
+    """n = 65 rows (one past a wave; 128 sort keys), R = 5 replicates: y has both classes, rows 10 / 20 / 30 tie in both probability
+    vectors, replicate 4 draws positives only."""
+    n, R = 65, 5
+    rng = np.random.default_rng(65)
+    y = (rng.random(n) < 0.4).astype(np.int64)
+    y[:2] = (0, 1)
+    base, probe = rng.random(n), rng.random(n)
+    base[[10, 20, 30]], probe[[10, 20, 30]] = 0.5, 0.625
+    index = np.stack([rng.integers(0, n, n) for _ in range(R)]).astype(np.int32)
+    index[1, :2] = (0, 1)                                                # both classes in the two rows the ragged form keeps of it
+    index[2] = rng.permutation(n)                                        # holds the whole tie group
+    index[4] = rng.choice(np.flatnonzero(y == 1), n)
+    return y, base, probe, index
+
+
+def _gains_ref(y, base, probe, replicates):
+    mb = np.array([binary_metrics_ref(y[i], base[i]) for i in replicates])
+    mp = np.array([binary_metrics_ref(y[i], probe[i]) for i in replicates])
+    both = ~np.isnan(mb[:, 1])
+    want = {}
+    for name, v in (("bce_gain", mb[:, 0] - mp[:, 0]), ("auroc_gain", (mp[:, 1] - mb[:, 1])[both]), ("auprc_gain", (mp[:, 2] - mb[:, 2])[both])):
+        want[f"{name}_ci_low"], want[f"{name}_ci_high"] = np.percentile(v, [2.5, 97.5])
+    return want, both
+
+
+def test_shared_resampling_statistics():
+    """probe_stats on the metrics kernel.  `paired_bootstrap_gains` returns intervals only, so the two forms of the index matrix are
+    compared on the replicates they share in two ways: the per-replicate kernel outputs at the shared positions of the two tables,
+    and the intervals of the shared replicates alone in either encoding.  Bounds: 1e-12 for one triple of 65 terms <= 16.2
+    (65 * 1.1e-16 * 16.2 ~ 1e-13), 1e-10 for the intervals (the bound of the metrics-kernel tests; percentiles interpolate linearly)."""
+    ps = _ps()
+    y, base, probe, index = _stats_case()
+    n, R = index.shape[1], len(index)
+    dev = torch.device(DEV)
+    d = lambda a: torch.as_tensor(a, device=dev)  # noqa: E731
+    # one triple: host array and device tensor
+    for p in (base, probe):
+        host, device = ps.binary_metrics(y, p, dev), ps.binary_metrics(y, d(p))
+        want = binary_metrics_ref(y, p)
+        print("binary_metrics", host, "deviation from the restatement", np.abs(np.array(list(host.values())) - want).max())
+        assert list(host) == list(device) == ["bce", "auroc", "auprc"]
+        assert all(host[k] == device[k] for k in host) and np.isfinite(list(host.values())).all()
+        np.testing.assert_allclose(list(host.values()), want, rtol=1e-12, atol=1e-12)
+    one = ps.binary_metrics(y[index[4]], d(base[index[4]]))                # one class: BCE only, NaN at the same places in both forms
+    assert np.isfinite(one["bce"]) and np.isnan(one["auroc"]) and np.isnan(one["auprc"])
+    assert np.array_equal(np.isnan(list(ps.binary_metrics(y[index[4]], base[index[4]], dev).values())), [False, True, True])
+    # the intervals: rectangular and ragged index tables
+    rect_off = torch.arange(0, (R + 1) * n, n, dtype=torch.int64, device=dev)
+    rect = ps.paired_bootstrap_gains(y, base, probe, index.reshape(-1), rect_off, n, dev)
+    ragged_rows = [index[0][:64], index[1][:2], index[2], index[3], index[4]]
+    ragged_idx = np.concatenate(ragged_rows)
+    ragged_off = np.cumsum([0] + [len(r) for r in ragged_rows]).astype(np.int64)
+    ragged = ps.paired_bootstrap_gains(y, base, probe, ragged_idx, ragged_off, 65, dev)
+    for name, got, replicates in (("rectangular", rect, list(index)), ("ragged", ragged, ragged_rows)):
+        want, both = _gains_ref(y, base, probe, replicates)
+        assert both.tolist() == [True, True, True, True, False] and list(got) == list(want) == CI_KEYS
+        print(name, got, "largest deviation", np.abs(np.array(list(got.values())) - np.array(list(want.values()))).max())
+        np.testing.assert_allclose(list(got.values()), list(want.values()), rtol=1e-10, atol=1e-10)
+    shared = slice(2, 5)
+    for p in (base, probe):                                               # the shared replicates, at other offsets beside other neighbours
+        a = ps.resampled_binary_metrics(d(y.astype(np.uint8)), d(p[None]), d(index.reshape(-1)), rect_off, n).cpu().numpy()
+        b = ps.resampled_binary_metrics(d(y.astype(np.uint8)), d(p[None]), d(ragged_idx), d(ragged_off), 65).cpu().numpy()
+        assert np.array_equal(a[shared], b[shared], equal_nan=True) and np.isnan(a[4, 1:]).all() and np.isfinite(a[:4]).all()
+    shared_rect = ps.paired_bootstrap_gains(y, base, probe, index[shared].reshape(-1), rect_off[:4], n, dev)
+    shared_ragged = ps.paired_bootstrap_gains(y, base, probe, ragged_idx[ragged_off[2]:], ragged_off[2:] - ragged_off[2], 65, dev)
+    assert list(shared_rect.values()) == list(shared_ragged.values()) and np.isfinite(list(shared_rect.values())).all()
+    # no replicate
+    for nothing in (None, torch.empty((0, n), dtype=torch.float64, device=dev)):
+        empty = ps.permutation_summary(y, nothing)
+        assert list(empty) == PERM_KEYS and all(np.isnan(v) for v in empty.values())
+    none = ps.paired_bootstrap_gains(y, base, probe, np.zeros(0, np.int32), np.zeros(1, np.int64), 0, dev)
+    assert list(none) == CI_KEYS and all(np.isnan(v) for v in none.values())

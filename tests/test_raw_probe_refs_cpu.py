@@ -1,6 +1,6 @@
 """CPU: the numpy restatement of the raw-trajectory-probe kernels (tests/raw_probe_refs.py) is pinned on the reference's own outputs
 (tests/golden/raw_probe.npz, written by tests/golden/make_golden_raw_probe.py), and the host-side index draws of
-multimodal_edema_prediction_amd.raw_trajectory_probe equal the reference's.
+multimodal_edema_prediction_amd.probe_stats equal the reference's.
 
 Tolerances.  The restatement and the reference both work in fp64 and differ only in summation order (numpy's pairwise / blocked sums
 against hour-by-hour sums; BLAS dot products against numpy's), so the bound is the fp64 rounding of sums of <= 240 terms of magnitude
@@ -67,7 +67,7 @@ def test_metrics_restatement_on_ties_against_sklearn():
 
 
 def test_host_index_draws_equal_the_reference():
-    from multimodal_edema_prediction_amd import raw_trajectory_probe as rp
+    from multimodal_edema_prediction_amd import probe_stats as rp
     g = golden()
     boot_seed = perm_seed = int(g["cfg"][7])                            # the level block is probe_offset 0
     idx, offsets = rp.draw_cluster_bootstrap_indices(g["subject_test"], int(g["cfg"][8]), boot_seed)

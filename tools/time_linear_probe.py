@@ -13,7 +13,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
-from multimodal_edema_prediction_amd import head_probe, unimodal_linear_probe as ulp
+from multimodal_edema_prediction_amd import head_probe, probe_stats, unimodal_linear_probe as ulp
 
 EPOCHS = int(sys.argv[1]) if len(sys.argv) > 1 else 300
 N_TR, N_VA, L, BS, WIDTHS = 20_000, 4_000, 7, 128, (768, 1176, 4704)
@@ -65,12 +65,12 @@ print(f"  head_train_epoch P = 3, the three widths in one launch  : {t:8.3f} ms 
 for F in WIDTHS:
     pb = problem(F)
     _, (Xv, Yv, Mv) = data[F]
-    metrics = head_probe.LabelMetrics(Yv, Mv)
+    metrics = probe_stats.LabelMetrics(Yv, Mv)
     best = {"v": torch.full((), -float("inf"), dtype=torch.float64, device=dev), "W": pb.W.clone()}
 
     def select():
         _, probs = head_probe.head_scores(Xv, pb.W, pb.b)
-        macro = head_probe.nan_mean(metrics(probs)[:, 1])
+        macro = probe_stats.nan_mean(metrics(probs)[:, 1])
         better = macro > best["v"]
         best["v"] = torch.where(better, macro, best["v"])
         best["W"] = torch.where(better, pb.W, best["W"])

@@ -10,7 +10,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
-from multimodal_edema_prediction_amd import raw_trajectory_probe as rp
+from multimodal_edema_prediction_amd import probe_stats, raw_trajectory_probe as rp
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 T, V, RECENT, HBM_PEAK = 96, 48, 6, 8.0e12
@@ -67,11 +67,11 @@ floor_ms = n * F * 8 / HBM_PEAK * 1e3
 print(f"offset_logistic_valgrad  : {ms:9.4f} ms per evaluation  (n = {n}, F = {F}, G = {G}; bytes(X) = {n * F * 8 / 1e6:.1f} MB, "
       f"bytes(X) / 8 TB/s = {floor_ms:.4f} ms, ratio {ms / floor_ms:.1f}; workspace {ws.numel() * 8 / 1e6:.1f} MB)")
 
-idx, offsets = rp.draw_cluster_bootstrap_indices(subj_te, 1000, 42)
+idx, offsets = probe_stats.draw_cluster_bootstrap_indices(subj_te, 1000, 42)
 yu, idx_d, off_d = torch.as_tensor(y_te.astype(np.uint8), device=dev), torch.as_tensor(idx, device=dev), torch.as_tensor(offsets, device=dev)
 p = torch.sigmoid(torch.as_tensor(img_te, dtype=torch.float64, device=dev))[None]
 longest = int(np.diff(offsets).max())
-print(f"resampled_binary_metrics : {timed(lambda: rp.resampled_binary_metrics(yu, p, idx_d, off_d, longest), 10):9.3f} ms   "
+print(f"resampled_binary_metrics : {timed(lambda: probe_stats.resampled_binary_metrics(yu, p, idx_d, off_d, longest), 10):9.3f} ms   "
       f"(1000 bootstrap replicates, longest {longest})")
 
 torch.cuda.synchronize()
