@@ -12,6 +12,7 @@
 // with ScaleNorm emitting bf16 straight into the MFMA GEMMs and both residual adds fused in GEMM epilogues.
 #include "common.h"
 #include "medp_hip.h"
+#include "norm_rows.h"
 
 namespace {
 
@@ -292,8 +293,8 @@ __global__ __launch_bounds__(256) void axis_swap_add_kernel(const float* __restr
 // One workgroup per event-view row (b, v): its T+1 cells are CONTIGUOUS in the event view ((T+1)*E floats), so the row is
 // assembled in LDS and leaves in whole-row coalesced 16-B stores — the time-view psi kernel above writes 96-B cells 4.7 KB apart.
 // It replaces psi_embed + axis_swap_add + scalenorm of layer 0 (psi0 is never written; reads 2.4 MB, writes |psi| fp32 + bf16).
-// The row's sum of squares is taken by wave 0 in the lane / chunk order of scalenorm_fwd_reg_kernel, so `h` is bit-identical to
-// what the separate ScaleNorm launch produced.
+// The row's norm is scalenorm_rn over the LDS tile: the re-read form of norm_rows.h, which agrees with the register form of the
+// separate ScaleNorm launch up to the rounding of a row's sum; the bf16 `h` has equalled it in every tested case.
 struct TabWeights {
     const float *xs, *w0, *b0, *s, *sh, *w4, *b4;
     int Ds, Hd;
@@ -494,16 +495,10 @@ __global__ __launch_bounds__(128) void psi_embed_event_kernel(const float* __res
         }
     }
     __syncthreads();
-    {   // row norms: wave w takes rows w, w+2 in the canonical order (lane + 64 k, then the wave tree) of scalenorm_fwd_reg_kernel
+    {   // row norms: wave w takes rows w, w+2
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         for (int bb = wave; bb < nb; bb += 2) {
-            const float* tb = tile + (size_t)bb * D;
-            float ss = 0.f;
-            for (int i = lane; i < D4; i += 64) {
-                const float4 x = *(const float4*)(tb + 4 * i);
-                ss += (x.x * x.x + x.y * x.y) + (x.z * x.z + x.w * x.w);
-            }
-            const float rn = 1.0f / fmaxf(sqrtf(wave_sum(ss)), norm_eps);
+            const float rn = scalenorm_rn(RowReread(lane, D, tile + (size_t)bb * D), norm_eps);
             if (lane == 0) s_rn[bb] = rn;
         }
     }
@@ -514,17 +509,15 @@ __global__ __launch_bounds__(128) void psi_embed_event_kernel(const float* __res
         const float sc = s_rn[bb] * sqrtf((float)D) * g_norm[0];
         for (int i = threadIdx.x; i < D4; i += 128) {
             const float4 x = *(const float4*)(tb + 4 * i);
-            uint2 o;
-            o.x = pack_bf2(x.x * sc, x.y * sc);
-            o.y = pack_bf2(x.z * sc, x.w * sc);
-            *(uint2*)(h + rbase + 4 * i) = o;
+            store_row4<true>(h + rbase, i, x.x * sc, x.y * sc, x.z * sc, x.w * sc);
         }
     }
 }
 
 // ---- axis swap + positional add + the NEXT encoder's first ScaleNorm in one pass (wave per output row, row in registers) --------
 // x[b][a2][a1][:] = in[b][a1][a2][:] * rowscale(b, a1) + add ;  h = ScaleNorm(x) as bf16.  One read of psi, one fp32 + one bf16
-// write, instead of swap (read + write) then ScaleNorm (read + write).  Lane / chunk order of scalenorm_fwd_reg_kernel: bit-identical.
+// write, instead of swap (read + write) then ScaleNorm (read + write).  The row holder and the ScaleNorm tail are those of
+// scalenorm_fwd_reg_kernel (norm_rows.h): bit-identical.
 template <int NV>
 __global__ __launch_bounds__(256) void swap_add_norm_kernel(const float* __restrict__ in, const float* __restrict__ rnorm,
                                                             const float* __restrict__ g_prev, float gain_sqrt_dim,
@@ -535,51 +528,30 @@ __global__ __launch_bounds__(256) void swap_add_norm_kernel(const float* __restr
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= B * A2) return;
     const int b = row / A2, a2 = row - b * A2;
-    const int D4 = A1 * E4, D = D4 * 4;
+    const int D = A1 * E4 * 4;
     const float gain = rnorm ? gain_sqrt_dim * g_prev[0] : 1.f;
     const float* addr = add + (size_t)b * add_bs + (size_t)a2 * D;
-    float4 v[NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = lane + 64 * k;
-        v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < D4) {
-            const int a1 = i / E4, e4 = i - a1 * E4;
-            const float4 s = *(const float4*)(in + ((((size_t)b * A1 + a1) * A2 + a2) * E4 + e4) * 4);
-            const float sc = rnorm ? rnorm[(size_t)b * A1 + a1] * gain : 1.f;
-            const float4 ad = *(const float4*)(addr + 4 * i);
-            v[k] = make_float4(s.x * sc + ad.x, s.y * sc + ad.y, s.z * sc + ad.z, s.w * sc + ad.w);
-            *(float4*)(x_out + (size_t)row * D + 4 * i) = v[k];
-        }
-    }
-    float ss = 0.f;
-#pragma unroll
-    for (int k = 0; k < NV; ++k)
-        if (lane + 64 * k < D4) ss += (v[k].x * v[k].x + v[k].y * v[k].y) + (v[k].z * v[k].z + v[k].w * v[k].w);
-    const float rn = 1.0f / fmaxf(sqrtf(wave_sum(ss)), norm_eps);
-    const float sc = rn * sqrtf((float)D) * g_norm[0];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = lane + 64 * k;
-        if (i < D4) {
-            uint2 o;
-            o.x = pack_bf2(v[k].x * sc, v[k].y * sc);
-            o.y = pack_bf2(v[k].z * sc, v[k].w * sc);
-            *(uint2*)(h_out + (size_t)row * D + 4 * i) = o;
-        }
-    }
+    float* xrow = x_out + (size_t)row * D;
+    const RowRegs<NV> x(lane, D, [&](int i) {
+        const int a1 = i / E4, e4 = i - a1 * E4;
+        const float4 s = *(const float4*)(in + ((((size_t)b * A1 + a1) * A2 + a2) * E4 + e4) * 4);
+        const float sc = rnorm ? rnorm[(size_t)b * A1 + a1] * gain : 1.f;
+        const float4 ad = *(const float4*)(addr + 4 * i);
+        const float4 v = make_float4(s.x * sc + ad.x, s.y * sc + ad.y, s.z * sc + ad.z, s.w * sc + ad.w);
+        *(float4*)(xrow + 4 * i) = v;
+        return v;
+    });
+    scalenorm_fwd_row<true>(x, g_norm, norm_eps, h_out, D, nullptr, row);
 }
 
 int launch_swap_add_norm(const float* in, const float* rnorm, const float* g_prev, float gain_sqrt_dim, const float* add, long long add_bs,
                          const float* g_norm, float norm_eps, float* x_out, void* h_out, int B, int A1, int A2, int E4, hipStream_t s) {
     const int nv = (A1 * E4 + 63) / 64, grid = (B * A2 + 3) / 4;
-#define MEDP_SAN(NV) swap_add_norm_kernel<NV><<<grid, 256, 0, s>>>(in, rnorm, g_prev, gain_sqrt_dim, add, add_bs, g_norm, norm_eps, x_out, (bf16_t*)h_out, B, A1, A2, E4)
-    if (nv <= 5) MEDP_SAN(5);
-    else if (nv <= 10) MEDP_SAN(10);
-    else if (nv <= 16) MEDP_SAN(16);
-    else if (nv <= 25) MEDP_SAN(25);
-    else return 1;          // wider rows: the caller takes the two-launch path
-#undef MEDP_SAN
+    if (!dispatch_nv<5, 10, 16, 25>(nv, [&](auto NV) {
+            swap_add_norm_kernel<decltype(NV)::value><<<grid, 256, 0, s>>>(in, rnorm, g_prev, gain_sqrt_dim, add, add_bs, g_norm, norm_eps, x_out,
+                                                                          (bf16_t*)h_out, B, A1, A2, E4);
+        }))
+        return 1;          // wider rows: the caller takes the two-launch path
     MEDP_LAUNCH_CHECK("duett swap+add+norm");
     return 0;
 }

@@ -1,11 +1,15 @@
 // Row normalisations for gfx950: LayerNorm (ViT, perceiver) and ScaleNorm (DuETT encoders), forward + backward.
-// HBM-bound: one 64-lane wave per row, float4 loads, wavefront shuffle reductions, statistics in fp32.
-// The row is read from HBM once (the second/third sweep of the same wave hits L1/L2); the output is written
-// as bf16 when it feeds an MFMA GEMM, as fp32 when it is a residual stream.
+// HBM-bound: one 64-lane wave per row, float4 loads, wavefront shuffle reductions, statistics in fp32; bf16 output when it feeds an
+// MFMA GEMM, fp32 when it is a residual stream.  A wave holds its row in registers (*_reg_kernel) or re-reads it on every sweep:
+// the two holders, the summation order, the rounding of the products, the row store and the NV dispatch are in norm_rows.h.
+// ScaleNorm forward and backward are one body each over either holder.  LayerNorm forward is NOT: its kernels leave the fusion of
+// (a a + c c) + (d d + e e) to the compiler, which chooses per instantiation (<., 3>: fused in the first two of the three float4,
+// rounded in the third), so no holder-wide rule reproduces them and pinning one moves the ViT's rstd: they keep their text.
 #include <stdlib.h>
 
 #include "common.h"
 #include "medp_hip.h"
+#include "norm_rows.h"
 
 namespace {
 
@@ -18,44 +22,32 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* xr = x + (size_t)row * ldx;
-    const int D4 = D >> 2;
+    const RowReread r(lane, D, x + (size_t)row * ldx);
     float s = 0.f;
-    for (int i = lane; i < D4; i += 64) {
-        const float4 v = *(const float4*)(xr + 4 * i);
-        s += (v.x + v.y) + (v.z + v.w);
-    }
+    r.each([&](int, float4 v) { s += (v.x + v.y) + (v.z + v.w); });
     const float mean = wave_sum(s) / (float)D;
     float ss = 0.f;
-    for (int i = lane; i < D4; i += 64) {
-        const float4 v = *(const float4*)(xr + 4 * i);
+    r.each([&](int, float4 v) {
         const float a = v.x - mean, c = v.y - mean, d = v.z - mean, e = v.w - mean;
         ss += (a * a + c * c) + (d * d + e * e);
-    }
+    });
     const float rstd = rsqrtf(wave_sum(ss) / (float)D + eps);
     if (lane == 0) {
         if (mean_out) mean_out[row] = mean;
         if (rstd_out) rstd_out[row] = rstd;
     }
-    for (int i = lane; i < D4; i += 64) {
-        const float4 v = *(const float4*)(xr + 4 * i);
+    void* yrow = row_ptr<OUT_BF16>(y, (size_t)row * ldy);
+    r.each([&](int i, float4 v) {
         const float4 ww = *(const float4*)(w + 4 * i);
         const float4 bb = *(const float4*)(b + 4 * i);
-        const float o0 = (v.x - mean) * rstd * ww.x + bb.x, o1 = (v.y - mean) * rstd * ww.y + bb.y;
-        const float o2 = (v.z - mean) * rstd * ww.z + bb.z, o3 = (v.w - mean) * rstd * ww.w + bb.w;
-        if (OUT_BF16) {
-            uint2 o;
-            o.x = pack_bf2(o0, o1);
-            o.y = pack_bf2(o2, o3);
-            *(uint2*)((bf16_t*)y + (size_t)row * ldy + 4 * i) = o;
-        } else {
-            *(float4*)((float*)y + (size_t)row * ldy + 4 * i) = make_float4(o0, o1, o2, o3);
-        }
-    }
+        store_row4<OUT_BF16>(yrow, i, (v.x - mean) * rstd * ww.x + bb.x, (v.y - mean) * rstd * ww.y + bb.y,
+                             (v.z - mean) * rstd * ww.z + bb.z, (v.w - mean) * rstd * ww.w + bb.w);
+    });
 }
 
 // Register-resident variant for D == 256*NV (ViT: NV=3, perceiver: NV=1): each lane keeps its NV float4 of the row, so the
-// row crosses the memory pipeline exactly once.  Same per-lane summation order as the generic kernel (bit-identical).
+// row crosses the memory pipeline exactly once.  Same per-lane summation order as the generic kernel (not the same fusion of the
+// products: see the top of this file), so it keeps its own loops.
 template <bool OUT_BF16, int NV>
 __global__ __launch_bounds__(256) void layernorm_fwd_reg_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w,
                                                                 const float* __restrict__ b, void* __restrict__ y, int ldy,
@@ -89,16 +81,8 @@ __global__ __launch_bounds__(256) void layernorm_fwd_reg_kernel(const float* __r
         const int i = lane + 64 * j;
         const float4 ww = *(const float4*)(w + 4 * i);
         const float4 bb = *(const float4*)(b + 4 * i);
-        const float o0 = (v[j].x - mean) * rstd * ww.x + bb.x, o1 = (v[j].y - mean) * rstd * ww.y + bb.y;
-        const float o2 = (v[j].z - mean) * rstd * ww.z + bb.z, o3 = (v[j].w - mean) * rstd * ww.w + bb.w;
-        if (OUT_BF16) {
-            uint2 o;
-            o.x = pack_bf2(o0, o1);
-            o.y = pack_bf2(o2, o3);
-            *(uint2*)((bf16_t*)y + (size_t)row * ldy + 4 * i) = o;
-        } else {
-            *(float4*)((float*)y + (size_t)row * ldy + 4 * i) = make_float4(o0, o1, o2, o3);
-        }
+        store_row4<OUT_BF16>(row_ptr<OUT_BF16>(y, (size_t)row * ldy), i, (v[j].x - mean) * rstd * ww.x + bb.x, (v[j].y - mean) * rstd * ww.y + bb.y,
+                             (v[j].z - mean) * rstd * ww.z + bb.z, (v[j].w - mean) * rstd * ww.w + bb.w);
     }
 }
 
@@ -111,22 +95,20 @@ __global__ __launch_bounds__(256) void layernorm_bwd_dx_kernel(const float* __re
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* xr = x + (size_t)row * ldx;
-    const float* gr = dy + (size_t)row * lddy;
+    const RowReread xr(lane, D, x + (size_t)row * ldx), gr(lane, D, dy + (size_t)row * lddy);
     const float mu = mean[row], rs = rstd[row];
-    const int D4 = D >> 2;
     float s1 = 0.f, s2 = 0.f;
-    for (int i = lane; i < D4; i += 64) {
-        const float4 v = *(const float4*)(xr + 4 * i), g = *(const float4*)(gr + 4 * i), ww = *(const float4*)(w + 4 * i);
+    xr.each(gr, [&](int i, float4 v, float4 g) {
+        const float4 ww = *(const float4*)(w + 4 * i);
         const float g0 = g.x * ww.x, g1 = g.y * ww.y, g2 = g.z * ww.z, g3 = g.w * ww.w;
         s1 += (g0 + g1) + (g2 + g3);
         s2 += (g0 * (v.x - mu) + g1 * (v.y - mu)) + (g2 * (v.z - mu) + g3 * (v.w - mu));
-    }
+    });
     s1 = wave_sum(s1) / (float)D;
     s2 = wave_sum(s2) * rs / (float)D;   // mean(g * xhat)
     float* dr = dx + (size_t)row * lddx;
-    for (int i = lane; i < D4; i += 64) {
-        const float4 v = *(const float4*)(xr + 4 * i), g = *(const float4*)(gr + 4 * i), ww = *(const float4*)(w + 4 * i);
+    xr.each(gr, [&](int i, float4 v, float4 g) {
+        const float4 ww = *(const float4*)(w + 4 * i);
         float4 o;
         o.x = rs * (g.x * ww.x - s1 - (v.x - mu) * rs * s2);
         o.y = rs * (g.y * ww.y - s1 - (v.y - mu) * rs * s2);
@@ -137,7 +119,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_dx_kernel(const float* __re
             o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
         }
         *(float4*)(dr + 4 * i) = o;
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ column reductions
@@ -202,32 +184,11 @@ __global__ __launch_bounds__(256) void scalenorm_fwd_kernel(const float* __restr
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* xr = x + (size_t)row * ldx;
-    const int D4 = D >> 2;
-    float ss = 0.f;
-    for (int i = lane; i < D4; i += 64) {
-        const float4 v = *(const float4*)(xr + 4 * i);
-        ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-    }
-    const float rn = 1.0f / fmaxf(sqrtf(wave_sum(ss)), eps);
-    if (lane == 0 && rnorm_out) rnorm_out[row] = rn;
-    const float sc = rn * sqrtf((float)D) * g[0];
-    for (int i = lane; i < D4; i += 64) {
-        const float4 v = *(const float4*)(xr + 4 * i);
-        if (OUT_BF16) {
-            uint2 o;
-            o.x = pack_bf2(v.x * sc, v.y * sc);
-            o.y = pack_bf2(v.z * sc, v.w * sc);
-            *(uint2*)((bf16_t*)y + (size_t)row * ldy + 4 * i) = o;
-        } else {
-            *(float4*)((float*)y + (size_t)row * ldy + 4 * i) = make_float4(v.x * sc, v.y * sc, v.z * sc, v.w * sc);
-        }
-    }
+    scalenorm_fwd_row<OUT_BF16>(RowReread(lane, D, x + (size_t)row * ldx), g, eps, y, ldy, rnorm_out, row);
 }
 
-// The same with the row held in registers (D <= 4 * 64 * NV): ONE pass over memory and NV independent 16-B loads in flight per
-// lane.  The two-pass kernel above keeps one load per wave in flight: at D = 2328 (DuETT's event-axis tokens, 29 MB per call)
-// it ran at 1.9 TB/s, this one is bound by HBM.  Same per-lane summation order: the results are bit-identical.
+// The same with the row held in registers (D <= 4 * 64 * NV, body in norm_rows.h): ONE pass over memory, NV independent 16-B loads in
+// flight per lane.  The two-pass kernel above keeps one in flight: 1.9 TB/s at D = 2328 (29 MB per call); this one is bound by HBM.
 template <bool OUT_BF16, int NV>
 __global__ __launch_bounds__(256) void scalenorm_fwd_reg_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ g,
                                                                 void* __restrict__ y, int ldy, float* __restrict__ rnorm_out,
@@ -235,35 +196,7 @@ __global__ __launch_bounds__(256) void scalenorm_fwd_reg_kernel(const float* __r
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float* xr = x + (size_t)row * ldx;
-    const int D4 = D >> 2;
-    float4 v[NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = lane + 64 * k;
-        v[k] = i < D4 ? *(const float4*)(xr + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float ss = 0.f;
-#pragma unroll
-    for (int k = 0; k < NV; ++k)
-        if (lane + 64 * k < D4) ss += (v[k].x * v[k].x + v[k].y * v[k].y) + (v[k].z * v[k].z + v[k].w * v[k].w);
-    const float rn = 1.0f / fmaxf(sqrtf(wave_sum(ss)), eps);
-    if (lane == 0 && rnorm_out) rnorm_out[row] = rn;
-    const float sc = rn * sqrtf((float)D) * g[0];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int i = lane + 64 * k;
-        if (i < D4) {
-            if (OUT_BF16) {
-                uint2 o;
-                o.x = pack_bf2(v[k].x * sc, v[k].y * sc);
-                o.y = pack_bf2(v[k].z * sc, v[k].w * sc);
-                *(uint2*)((bf16_t*)y + (size_t)row * ldy + 4 * i) = o;
-            } else {
-                *(float4*)((float*)y + (size_t)row * ldy + 4 * i) = make_float4(v[k].x * sc, v[k].y * sc, v[k].z * sc, v[k].w * sc);
-            }
-        }
-    }
+    scalenorm_fwd_row<OUT_BF16>(RowRegs<NV>(lane, D, x + (size_t)row * ldx), g, eps, y, ldy, rnorm_out, row);
 }
 
 // dx = [acc_src +] s*rn*(dy - x*rn^2*<dy,x>),  s = sqrt(D)*g ;  dg_row = sqrt(D)*rn*<dy,x>   (summed over rows by sum_all_kernel).
@@ -271,40 +204,39 @@ __global__ __launch_bounds__(256) void scalenorm_fwd_reg_kernel(const float* __r
 // without touching the incoming gradient.  (Measured and rejected: the LAST workgroup finishing the dg sum behind a ticket — the
 // agent-scope fence every workgroup then needs writes back L2 1500 times per launch: student step 7.36 ms against 6.71,
 // profiles/r03_ab_experiments.txt section 12.)
+template <class Row>
+__device__ __forceinline__ void scalenorm_bwd_row(const Row& x, const Row& dy, const float* g, const float* rnorm, const float* acc_src,
+                                                  int ldacc, float* dx, int lddx, float* dg_rows, int row) {
+    float dot = 0.f;
+    x.each(dy, [&](int, float4 v, float4 d) { dot += Row::dot4(v, d); });
+    dot = wave_sum(dot);
+    const float rn = rnorm[row], sq = sqrtf((float)x.D);
+    if (x.lane == 0 && dg_rows) dg_rows[row] = sq * rn * dot;
+    const float s = sq * g[0] * rn, k = rn * rn * dot;
+    float* dr = dx + (size_t)row * lddx;
+    const float* ar = acc_src ? acc_src + (size_t)row * ldacc : nullptr;
+    x.each(dy, [&](int i, float4 v, float4 d) {
+        float4 o = make_float4(s * (d.x - v.x * k), s * (d.y - v.y * k), s * (d.z - v.z * k), s * (d.w - v.w * k));
+        if (ar) {
+            const float4 old = *(const float4*)(ar + 4 * i);
+            o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
+        }
+        *(float4*)(dr + 4 * i) = o;
+    });
+}
+
 __global__ __launch_bounds__(256) void scalenorm_bwd_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ x, int ldx,
                                                             const float* __restrict__ g, const float* __restrict__ rnorm, const float* acc_src,
                                                             int ldacc, float* dx, int lddx, float* dg_rows, int rows, int D) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    {
-        const float* xr = x + (size_t)row * ldx;
-        const float* gr = dy + (size_t)row * lddy;
-        const int D4 = D >> 2;
-        float dot = 0.f;
-        for (int i = lane; i < D4; i += 64) {
-            const float4 v = *(const float4*)(xr + 4 * i), d = *(const float4*)(gr + 4 * i);
-            dot += (v.x * d.x + v.y * d.y) + (v.z * d.z + v.w * d.w);
-        }
-        dot = wave_sum(dot);
-        const float rn = rnorm[row], sq = sqrtf((float)D);
-        if (lane == 0 && dg_rows) dg_rows[row] = sq * rn * dot;
-        const float s = sq * g[0] * rn, k = rn * rn * dot;
-        float* dr = dx + (size_t)row * lddx;
-        for (int i = lane; i < D4; i += 64) {
-            const float4 v = *(const float4*)(xr + 4 * i), d = *(const float4*)(gr + 4 * i);
-            float4 o = make_float4(s * (d.x - v.x * k), s * (d.y - v.y * k), s * (d.z - v.z * k), s * (d.w - v.w * k));
-            if (acc_src) {
-                const float4 old = *(const float4*)(acc_src + (size_t)row * ldacc + 4 * i);
-                o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
-            }
-            *(float4*)(dr + 4 * i) = o;
-        }
-    }
+    scalenorm_bwd_row(RowReread(lane, D, x + (size_t)row * ldx), RowReread(lane, D, dy + (size_t)row * lddy), g, rnorm, acc_src, ldacc, dx,
+                      lddx, dg_rows, row);
 }
 
-// The same with the row (x and dy) held in registers: one pass over the operands instead of two (D <= 256 NV floats).  The student
-// step runs this 13 times over 29-MB rowsets: 23 us with the two-pass kernel.
+// x and dy in registers (D <= 256 NV floats): one pass over the operands instead of two.  The student step runs this 13 times over
+// 29-MB rowsets: 23 us with the two-pass kernel.
 template <int NV>
 __global__ __launch_bounds__(256) void scalenorm_bwd_reg_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ x, int ldx,
                                                                 const float* __restrict__ g, const float* __restrict__ rnorm,
@@ -313,39 +245,8 @@ __global__ __launch_bounds__(256) void scalenorm_bwd_reg_kernel(const float* __r
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    {
-        const float* xr = x + (size_t)row * ldx;
-        const float* gr = dy + (size_t)row * lddy;
-        const int D4 = D >> 2;
-        float4 v[NV], d[NV];
-        float dot = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int i = lane + 64 * j;
-            const bool ok = i < D4;
-            v[j] = ok ? *(const float4*)(xr + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
-            d[j] = ok ? *(const float4*)(gr + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int j = 0; j < NV; ++j) dot += (v[j].x * d[j].x + v[j].y * d[j].y) + (v[j].z * d[j].z + v[j].w * d[j].w);
-        dot = wave_sum(dot);
-        const float rn = rnorm[row], sq = sqrtf((float)D);
-        if (lane == 0 && dg_rows) dg_rows[row] = sq * rn * dot;
-        const float s = sq * g[0] * rn, k = rn * rn * dot;
-        float* dr = dx + (size_t)row * lddx;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int i = lane + 64 * j;
-            if (i < D4) {
-                float4 o = make_float4(s * (d[j].x - v[j].x * k), s * (d[j].y - v[j].y * k), s * (d[j].z - v[j].z * k), s * (d[j].w - v[j].w * k));
-                if (acc_src) {
-                    const float4 old = *(const float4*)(acc_src + (size_t)row * ldacc + 4 * i);
-                    o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
-                }
-                *(float4*)(dr + 4 * i) = o;
-            }
-        }
-    }
+    scalenorm_bwd_row(RowRegs<NV>(lane, D, x + (size_t)row * ldx), RowRegs<NV>(lane, D, dy + (size_t)row * lddy), g, rnorm, acc_src, ldacc,
+                      dx, lddx, dg_rows, row);
 }
 
 __global__ __launch_bounds__(256) void sum_all_kernel(const float* __restrict__ v, float* __restrict__ out, int n) {
@@ -402,18 +303,14 @@ extern "C" int medp_layernorm_fwd(const float* x, int ldx, const float* w, const
     MEDP_CHECK_ARG(rows > 0 && D > 0 && D % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, "layernorm_fwd: D, ldx, ldy must be multiples of 4");
     dim3 grid((rows + 3) / 4);
     hipStream_t s = (hipStream_t)stream;
-    if (D == 768 && y_bf16)
-        layernorm_fwd_reg_kernel<true, 3><<<grid, 256, 0, s>>>(x, ldx, w, b, y, ldy, mean, rstd, rows, eps);
-    else if (D == 768)
-        layernorm_fwd_reg_kernel<false, 3><<<grid, 256, 0, s>>>(x, ldx, w, b, y, ldy, mean, rstd, rows, eps);
-    else if (D == 256 && y_bf16)
-        layernorm_fwd_reg_kernel<true, 1><<<grid, 256, 0, s>>>(x, ldx, w, b, y, ldy, mean, rstd, rows, eps);
-    else if (D == 256)
-        layernorm_fwd_reg_kernel<false, 1><<<grid, 256, 0, s>>>(x, ldx, w, b, y, ldy, mean, rstd, rows, eps);
-    else if (y_bf16)
-        layernorm_fwd_kernel<true><<<grid, 256, 0, s>>>(x, ldx, w, b, y, ldy, mean, rstd, rows, D, eps);
-    else
-        layernorm_fwd_kernel<false><<<grid, 256, 0, s>>>(x, ldx, w, b, y, ldy, mean, rstd, rows, D, eps);
+    auto launch = [&](auto bf) {
+        constexpr bool BF = decltype(bf)::value;
+        if (D == 768) layernorm_fwd_reg_kernel<BF, 3><<<grid, 256, 0, s>>>(x, ldx, w, b, y, ldy, mean, rstd, rows, eps);
+        else if (D == 256) layernorm_fwd_reg_kernel<BF, 1><<<grid, 256, 0, s>>>(x, ldx, w, b, y, ldy, mean, rstd, rows, eps);
+        else layernorm_fwd_kernel<BF><<<grid, 256, 0, s>>>(x, ldx, w, b, y, ldy, mean, rstd, rows, D, eps);
+    };
+    if (y_bf16) launch(std::true_type{});
+    else launch(std::false_type{});
     MEDP_LAUNCH_CHECK("medp_layernorm_fwd");
     return 0;
 }
@@ -469,20 +366,15 @@ extern "C" int medp_scalenorm_fwd(const float* x, int ldx, const float* g, void*
     dim3 grid((rows + 3) / 4);
     const int nv = (D / 4 + 63) / 64;
     hipStream_t st = (hipStream_t)stream;
-#define MEDP_SN_REG(NV)                                                                                             \
-    do {                                                                                                            \
-        if (y_bf16) scalenorm_fwd_reg_kernel<true, NV><<<grid, 256, 0, st>>>(x, ldx, g, y, ldy, rnorm, rows, D, eps);  \
-        else scalenorm_fwd_reg_kernel<false, NV><<<grid, 256, 0, st>>>(x, ldx, g, y, ldy, rnorm, rows, D, eps);       \
-    } while (0)
-    if (nv <= 2) MEDP_SN_REG(2);
-    else if (nv <= 5) MEDP_SN_REG(5);
-    else if (nv <= 10) MEDP_SN_REG(10);
-    else if (nv <= 16) MEDP_SN_REG(16);
-    else if (y_bf16)
-        scalenorm_fwd_kernel<true><<<grid, 256, 0, st>>>(x, ldx, g, y, ldy, rnorm, rows, D, eps);
-    else
-        scalenorm_fwd_kernel<false><<<grid, 256, 0, st>>>(x, ldx, g, y, ldy, rnorm, rows, D, eps);
-#undef MEDP_SN_REG
+    auto launch = [&](auto bf) {
+        constexpr bool BF = decltype(bf)::value;
+        if (!dispatch_nv<2, 5, 10, 16>(nv, [&](auto NV) {
+                scalenorm_fwd_reg_kernel<BF, decltype(NV)::value><<<grid, 256, 0, st>>>(x, ldx, g, y, ldy, rnorm, rows, D, eps);
+            }))
+            scalenorm_fwd_kernel<BF><<<grid, 256, 0, st>>>(x, ldx, g, y, ldy, rnorm, rows, D, eps);
+    };
+    if (y_bf16) launch(std::true_type{});
+    else launch(std::false_type{});
     MEDP_LAUNCH_CHECK("medp_scalenorm_fwd");
     return 0;
 }
@@ -496,9 +388,10 @@ static int scalenorm_bwd_launch(const float* dy, int lddy, const float* x, int l
     const int nv = (D / 4 + 63) / 64;
     float* dgr = dg ? workspace_rows : nullptr;
     const int grid = (rows + 3) / 4;
-    if (nv <= 5) scalenorm_bwd_reg_kernel<5><<<grid, 256, 0, s>>>(dy, lddy, x, ldx, g, rnorm, acc_src, ldacc, dx, lddx, dgr, rows, D);
-    else if (nv <= 10) scalenorm_bwd_reg_kernel<10><<<grid, 256, 0, s>>>(dy, lddy, x, ldx, g, rnorm, acc_src, ldacc, dx, lddx, dgr, rows, D);
-    else scalenorm_bwd_kernel<<<grid, 256, 0, s>>>(dy, lddy, x, ldx, g, rnorm, acc_src, ldacc, dx, lddx, dgr, rows, D);
+    if (!dispatch_nv<5, 10>(nv, [&](auto NV) {
+            scalenorm_bwd_reg_kernel<decltype(NV)::value><<<grid, 256, 0, s>>>(dy, lddy, x, ldx, g, rnorm, acc_src, ldacc, dx, lddx, dgr, rows, D);
+        }))
+        scalenorm_bwd_kernel<<<grid, 256, 0, s>>>(dy, lddy, x, ldx, g, rnorm, acc_src, ldacc, dx, lddx, dgr, rows, D);
     MEDP_LAUNCH_CHECK("medp_scalenorm_bwd");
     if (dg) {
         sum_all_kernel<<<1, 256, 0, s>>>(workspace_rows, dg, rows);

@@ -106,7 +106,7 @@ def test_gemm_rejects_bad_arguments():
 
 
 # ------------------------------------------------------------------------------------------------ norms
-@pytest.mark.parametrize("rows,D", [(5, 768), (1030, 256), (64 * 7, 256), (9, 2328)])
+@pytest.mark.parametrize("rows,D", [(5, 768), (1030, 256), (64 * 7, 256), (9, 2328), (5, 260)])      # 260: just past the register form
 def test_layernorm_fwd_bwd(rows, D):
     x = rnd(rows, D, seed=1) * 2 + 0.3
     w, b = 1 + 0.1 * rnd(D, seed=2), 0.1 * rnd(D, seed=3)
@@ -125,7 +125,10 @@ def test_layernorm_fwd_bwd(rows, D):
     assert_close(db, br.grad, 1e-4, 1e-4, "ln db")
 
 
-@pytest.mark.parametrize("rows,D", [(7, 408), (3136 // 8, 2328), (100, 1176), (9, 2564), (5, 6216)])      # 6216: the two-pass backward
+# 6216: the two-pass backward.  rows = 5 (not a multiple of the 4 rows per workgroup) on both sides of the register-width buckets
+# 2 / 5 / 10 / 16 (forward) and 5 / 10 (backward): 512 | 516, 1280 | 1284, 2560 | 2564, 4096 | 4100
+@pytest.mark.parametrize("rows,D", [(7, 408), (3136 // 8, 2328), (100, 1176), (9, 2564), (5, 6216),
+                                    (5, 512), (5, 516), (5, 1284), (5, 4096), (5, 4100)])
 def test_scalenorm_fwd_bwd(rows, D):
     x = rnd(rows, D, seed=1)
     g = torch.tensor([1.13])
@@ -147,6 +150,38 @@ def test_scalenorm_fwd_bwd(rows, D):
     check(lib().medp_scalenorm_bwd_add(ptr(dyd), D, ptr(xd), D, ptr(gd), ptr(rn), ptr(add), D, ptr(dx2), D, ptr(dg2), ptr(ws), rows, D, stream()), "bwd_add")
     assert torch.equal(add, add0)
     assert torch.equal(dx2, dx + add0) and torch.equal(dg2, dg)
+
+
+def test_norms_strided_input():
+    """A column slice of a wider tensor (ldx > D) gives the bits of the contiguous call."""
+    wide = rnd(5, 1176 + 8, seed=5).to(DEV)
+    g = torch.tensor([1.13], device=DEV)
+    for dt in (torch.float32, torch.bfloat16):
+        x = wide[:, :1176]
+        assert x.stride(0) == 1184
+        y, rn = Fn.scalenorm(x, g, out_dtype=dt, save_rnorm=True)
+        yc, rnc = Fn.scalenorm(x.contiguous(), g, out_dtype=dt, save_rnorm=True)
+        assert torch.equal(y, yc) and torch.equal(rn, rnc)
+        x = wide[:, :768]
+        w, b = (1 + 0.1 * rnd(768, seed=2)).to(DEV), (0.1 * rnd(768, seed=3)).to(DEV)
+        got = Fn.layernorm(x, w, b, 1e-5, out_dtype=dt, save_stats=True)
+        want = Fn.layernorm(x.contiguous(), w, b, 1e-5, out_dtype=dt, save_stats=True)
+        assert all(torch.equal(a, c) for a, c in zip(got, want))
+
+
+@pytest.mark.parametrize("D,Dpad", [(2560, 6216), (408, 1284)])      # register form, 10 float4 per lane -> re-read form; 2 -> 10
+def test_scalenorm_forms_agree(D, Dpad):
+    """The register and the re-read form of ScaleNorm forward walk a row in the same order (csrc/norm_rows.h): zero-padding the rows
+    on the right moves them to another form, adds exact zeros to each lane's partial sum and leaves lane assignment, pairing and the
+    wave tree as they were, and rnorm does not depend on D.  Both forms' product rounding is written out in the source, so the
+    outcome for these rows is fixed by the source, not by the compiler."""
+    x = rnd(5, D, seed=1).to(DEV)
+    g = torch.tensor([1.13], device=DEV)
+    xp = torch.zeros(5, Dpad, device=DEV)
+    xp[:, :D] = x
+    rn = Fn.scalenorm(x, g, save_rnorm=True)[1]
+    rnp = Fn.scalenorm(xp, g, save_rnorm=True)[1]
+    assert torch.equal(rn, rnp), f"{(rn != rnp).sum().item()} of 5 rnorm differ, max {(rn / rnp - 1).abs().max().item():.2e} relative"
 
 
 def test_colsum_and_cast_transpose():
