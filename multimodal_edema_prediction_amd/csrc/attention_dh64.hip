@@ -37,15 +37,6 @@ struct AttnParams {
     float* lse;  // optional [B, H, S]: log2-domain logsumexp of the scaled scores (training: consumed by the backward)
 };
 
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ bf16x4 lds_tr16(const char* addr) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(addr));
-}
-
 // max over the four lanes {fr, fr+16, fr+32, fr+48} that share a query column
 __device__ __forceinline__ float colmax4(float x) {
     auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);

@@ -31,13 +31,6 @@ struct BwdParams {
     int crows;
 };
 
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ bf16x4 lds_tr16(const char* addr) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(addr));
-}
 __device__ __forceinline__ bf16x8 pack8(const f32x4 a, const f32x4 b) {
     union { bf16x8 v; uint32_t u[4]; } pk;
     pk.u[0] = pack_bf2(a[0], a[1]);

@@ -10,6 +10,8 @@
 // Dropout on the probabilities uses the counter hash of common.h, regenerated in backward.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "attention_fq.h"
 #include "common.h"
 #include "medp_hip.h"
@@ -500,40 +502,86 @@ int check(const SmallAttnParams& p) {
     return 0;
 }
 
-// the wave-per-query launches, shared by the plain and the key-masked exports
-template <bool MASKED>
-void launch_small_fwd(const SmallAttnParams& p, void* o, int ldo, int o_bf16, float* attn_avg, hipStream_t st) {
+SmallAttnParams make_params(const float* q, int ldq, long long q_bs, const float* k, const float* v, int ldkv, long long kv_bs, int B, int Lq,
+                            int Lk, int H, int dh, float scale, float p, unsigned seed, unsigned stream_id,
+                            const unsigned char* mask = nullptr, long long mask_bs = 0) {
+    return SmallAttnParams{q, k, v, ldq, ldkv, ldkv, q_bs, kv_bs, B, Lq, Lk, H, dh, scale, p, 1.0f / (1.0f - p), seed, stream_id,
+                           medp_rng_epoch_ptr(), mask, mask_bs};
+}
+
+// ---- the launch tables: which instantiations are built, written once ----------------------------------------------------------------
+// f(std::integral_constant<int, N>) for the first N of NS... with n <= N (the last N if there is none); n < 0: for EVERY N in turn
+// (the per-kernel dynamic-LDS attributes)
+template <int... NS, typename F>
+void with_first(int n, F f) {
+    constexpr int last = (NS, ...);
+    bool done = false;
+    auto step = [&](auto N) {
+        if (done || !(n < 0 || n <= N() || N() == last)) return;
+        f(N);
+        done = n >= 0;
+    };
+    (step(std::integral_constant<int, NS>{}), ...);
+}
+// keys per lane of the wave-per-query kernels (forward, backward, head average)
+template <typename F> void with_nper(int nper, F f) { with_first<1, 2, 4, 8, MAXK_PER_LANE>(nper, f); }
+// chunks of FQ_T keys of the few-query pair
+template <typename F> void with_nch(int nch, F f) { with_first<1, 2, 4>(nch, f); }
+template <typename F> void with_masked(bool masked, F f) { if (masked) f(std::true_type{}); else f(std::false_type{}); }
+
+void set_max_lds(const void* kernel, int bytes) { hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
+
+size_t fq_lds(int nchp) { return (size_t)(2 * FQ * 64 + 4 * FQ + 16 * FQ * 64 + FQ * nchp * FQ_T) * sizeof(float); }
+size_t small_bwd_lds(const SmallAttnParams& p) { return (size_t)(2 * QCH * p.Lk + 2 * QCH * p.dh) * sizeof(float); }
+
+// The forward of the plain and the key-masked export (p.mask chooses).  Few queries without a mask and without a head average take
+// the thread-per-key kernels; everything else a wave per query, the masked form with its head average in a launch of its own.
+int small_fwd(const SmallAttnParams& p, void* o, int ldo, int o_bf16, float* attn_avg, hipStream_t st) {
+    const bool masked = p.mask != nullptr;
+    if (!masked && !attn_avg && fq_eligible(p, p.k, p.v, 4, 4)) {
+        MEDP_ONCE_PER_DEVICE({ with_nch(-1, [](auto NCH) { set_max_lds((const void*)attn_fq_fwd_kernel<NCH()>, 96 * 1024); }); });
+        with_nch((p.Lk + FQ_T - 1) / FQ_T, [&](auto NCH) { attn_fq_fwd_kernel<NCH()><<<p.B * p.H, FQ_T, fq_lds(NCH()), st>>>(p, o, ldo, o_bf16); });
+        MEDP_LAUNCH_CHECK("medp_attn_small_fwd(few queries)");
+        return 0;
+    }
     const size_t lds = (size_t)(4 * p.Lk + 4 * p.dh) * sizeof(float);
     const int nper = (p.Lk + 63) / 64;
     const dim3 grid(p.B * p.H, (p.Lq + FWD_QCH - 1) / FWD_QCH);
-    if (nper <= 1) attn_small_fwd_kernel<1, MASKED><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
-    else if (nper <= 2) attn_small_fwd_kernel<2, MASKED><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
-    else if (nper <= 4) attn_small_fwd_kernel<4, MASKED><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
-    else if (nper <= 8) attn_small_fwd_kernel<8, MASKED><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
-    else attn_small_fwd_kernel<MAXK_PER_LANE, MASKED><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, attn_avg);
+    with_masked(masked, [&](auto MASKED) {
+        with_nper(nper, [&](auto NPER) {
+            attn_small_fwd_kernel<NPER(), MASKED()><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, masked ? nullptr : attn_avg);
+        });
+    });
+    MEDP_LAUNCH_CHECK(masked ? "medp_attn_small_masked_fwd" : "medp_attn_small_fwd");
+    if (masked && attn_avg) {
+        with_nper(nper, [&](auto NPER) { attn_small_avg_kernel<NPER()><<<dim3(p.B, (p.Lq + 3) / 4), 256, 0, st>>>(p, attn_avg); });
+        MEDP_LAUNCH_CHECK("medp_attn_small_masked_fwd(attn_avg)");
+    }
+    return 0;
 }
 
-size_t small_bwd_lds(const SmallAttnParams& p) { return (size_t)(2 * QCH * p.Lk + 2 * QCH * p.dh) * sizeof(float); }
-
-template <bool MASKED>
-void launch_small_bwd(const SmallAttnParams& p, const float* dout, int lddo, float* dq, int lddq, float* dk, int lddk, float* dv,
-                      int lddv, long long dkv_bs, hipStream_t st) {
-    MEDP_ONCE_PER_DEVICE({
-        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<1, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<2, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<4, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<8, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipFuncSetAttribute((const void*)attn_small_bwd_kernel<MAXK_PER_LANE, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+// The backward of both exports.  dV has dK's row stride (both are column halves of one buffer).
+int small_bwd(const SmallAttnParams& p, const float* dout, int lddo, float* dq, int lddq, float* dk, int lddk, float* dv, long long dkv_bs,
+              hipStream_t st) {
+    const bool masked = p.mask != nullptr;
+    const int lddv = lddk, nb = p.B * p.H;
+    if (!masked && fq_eligible(p, dk, dv, lddk, lddv) && (dkv_bs & 3) == 0) {     // both gradient row strides: the kernel stores float4 rows of dK AND dV
+        MEDP_ONCE_PER_DEVICE({ with_nch(-1, [](auto NCH) { set_max_lds((const void*)attn_fq_bwd_kernel<NCH()>, 96 * 1024); }); });
+        with_nch((p.Lk + FQ_T - 1) / FQ_T, [&](auto NCH) {
+            attn_fq_bwd_kernel<NCH()><<<nb, FQ_T, fq_lds(NCH()), st>>>(p, dout, lddo, dq, lddq, dk, lddk, dv, lddv, dkv_bs);
+        });
+        MEDP_LAUNCH_CHECK("medp_attn_small_bwd(few queries)");
+        return 0;
+    }
+    MEDP_CHECK_ARG(small_bwd_lds(p) <= 160 * 1024, "%s: Lk too large for LDS", masked ? "attn_small_masked_bwd" : "attn_small_bwd");
+    with_masked(masked, [&](auto MASKED) {
+        MEDP_ONCE_PER_DEVICE({ with_nper(-1, [](auto NPER) { set_max_lds((const void*)attn_small_bwd_kernel<NPER(), decltype(MASKED)::value>, 160 * 1024); }); });
+        with_nper((p.Lk + 63) / 64, [&](auto NPER) {
+            attn_small_bwd_kernel<NPER(), MASKED()><<<nb, 256, small_bwd_lds(p), st>>>(p, dout, lddo, dq, lddq, dk, lddk, dv, lddv, dkv_bs);
+        });
     });
-    const size_t lds = small_bwd_lds(p);
-    const int nper = (p.Lk + 63) / 64, nb = p.B * p.H;
-#define MEDP_BWD_ARGS p, dout, lddo, dq, lddq, dk, lddk, dv, lddv, dkv_bs
-    if (nper <= 1) attn_small_bwd_kernel<1, MASKED><<<nb, 256, lds, st>>>(MEDP_BWD_ARGS);
-    else if (nper <= 2) attn_small_bwd_kernel<2, MASKED><<<nb, 256, lds, st>>>(MEDP_BWD_ARGS);
-    else if (nper <= 4) attn_small_bwd_kernel<4, MASKED><<<nb, 256, lds, st>>>(MEDP_BWD_ARGS);
-    else if (nper <= 8) attn_small_bwd_kernel<8, MASKED><<<nb, 256, lds, st>>>(MEDP_BWD_ARGS);
-    else attn_small_bwd_kernel<MAXK_PER_LANE, MASKED><<<nb, 256, lds, st>>>(MEDP_BWD_ARGS);
-#undef MEDP_BWD_ARGS
+    MEDP_LAUNCH_CHECK(masked ? "medp_attn_small_masked_bwd" : "medp_attn_small_bwd");
+    return 0;
 }
 
 }  // namespace
@@ -541,59 +589,21 @@ void launch_small_bwd(const SmallAttnParams& p, const float* dout, int lddo, flo
 extern "C" int medp_attn_small_fwd(const float* q, int ldq, long long q_batch_stride, const float* k, const float* v, int ldkv,
                                    long long kv_batch_stride, void* o, int ldo, int o_bf16, float* attn_avg, int B, int Lq, int Lk,
                                    int H, int dh, float scale, float dropout_p, unsigned seed, unsigned stream_id, void* stream) {
-    SmallAttnParams p{q, k, v, ldq, ldkv, ldkv, q_batch_stride, kv_batch_stride, B, Lq, Lk, H, dh, scale, dropout_p, 1.0f / (1.0f - dropout_p), seed, stream_id, medp_rng_epoch_ptr()};
+    const SmallAttnParams p = make_params(q, ldq, q_batch_stride, k, v, ldkv, kv_batch_stride, B, Lq, Lk, H, dh, scale, dropout_p, seed, stream_id);
     MEDP_TRY(check(p));
     MEDP_CHECK_ARG(o, "attn_small_fwd: null output");
-    hipStream_t st = (hipStream_t)stream;
-    if (!attn_avg && fq_eligible(p, k, v, 4, 4)) {
-        const int nch = (Lk + FQ_T - 1) / FQ_T;
-        const int nchp = nch <= 1 ? 1 : (nch <= 2 ? 2 : 4);
-        const size_t fl = (size_t)(2 * FQ * 64 + 4 * FQ + 16 * FQ * 64 + FQ * nchp * FQ_T) * sizeof(float);
-        MEDP_ONCE_PER_DEVICE({
-            hipFuncSetAttribute((const void*)attn_fq_fwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            hipFuncSetAttribute((const void*)attn_fq_fwd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            hipFuncSetAttribute((const void*)attn_fq_fwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        });
-        if (nchp == 1) attn_fq_fwd_kernel<1><<<B * H, FQ_T, fl, st>>>(p, o, ldo, o_bf16);
-        else if (nchp == 2) attn_fq_fwd_kernel<2><<<B * H, FQ_T, fl, st>>>(p, o, ldo, o_bf16);
-        else attn_fq_fwd_kernel<4><<<B * H, FQ_T, fl, st>>>(p, o, ldo, o_bf16);
-        MEDP_LAUNCH_CHECK("medp_attn_small_fwd(few queries)");
-        return 0;
-    }
-    launch_small_fwd<false>(p, o, ldo, o_bf16, attn_avg, st);
-    MEDP_LAUNCH_CHECK("medp_attn_small_fwd");
-    return 0;
+    return small_fwd(p, o, ldo, o_bf16, attn_avg, (hipStream_t)stream);
 }
 
 extern "C" int medp_attn_small_bwd(const float* dout, int lddo, const float* q, int ldq, long long q_batch_stride, const float* k,
                                    const float* v, int ldkv, long long kv_batch_stride, float* dq, int lddq, float* dk, int lddk,
                                    float* dv, int lddkv_unused, long long dkv_batch_stride, int B, int Lq, int Lk, int H, int dh,
                                    float scale, float dropout_p, unsigned seed, unsigned stream_id, void* stream) {
-    const int lddv = lddk;
     (void)lddkv_unused;
-    SmallAttnParams p{q, k, v, ldq, ldkv, ldkv, q_batch_stride, kv_batch_stride, B, Lq, Lk, H, dh, scale, dropout_p, 1.0f / (1.0f - dropout_p), seed, stream_id, medp_rng_epoch_ptr()};
+    const SmallAttnParams p = make_params(q, ldq, q_batch_stride, k, v, ldkv, kv_batch_stride, B, Lq, Lk, H, dh, scale, dropout_p, seed, stream_id);
     MEDP_TRY(check(p));
     MEDP_CHECK_ARG(dout && dq && dk && dv, "attn_small_bwd: null gradient buffer");
-    if (fq_eligible(p, dk, dv, lddk, lddv) && (dkv_batch_stride & 3) == 0) {     // both gradient row strides: the kernel stores float4 rows of dK AND dV
-        const int nch = (Lk + FQ_T - 1) / FQ_T;
-        const int nchp = nch <= 1 ? 1 : (nch <= 2 ? 2 : 4);
-        const size_t fl = (size_t)(2 * FQ * 64 + 4 * FQ + 16 * FQ * 64 + FQ * nchp * FQ_T) * sizeof(float);
-        MEDP_ONCE_PER_DEVICE({
-            hipFuncSetAttribute((const void*)attn_fq_bwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            hipFuncSetAttribute((const void*)attn_fq_bwd_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            hipFuncSetAttribute((const void*)attn_fq_bwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        });
-        hipStream_t fs = (hipStream_t)stream;
-        if (nchp == 1) attn_fq_bwd_kernel<1><<<B * H, FQ_T, fl, fs>>>(p, dout, lddo, dq, lddq, dk, lddk, dv, lddv, dkv_batch_stride);
-        else if (nchp == 2) attn_fq_bwd_kernel<2><<<B * H, FQ_T, fl, fs>>>(p, dout, lddo, dq, lddq, dk, lddk, dv, lddv, dkv_batch_stride);
-        else attn_fq_bwd_kernel<4><<<B * H, FQ_T, fl, fs>>>(p, dout, lddo, dq, lddq, dk, lddk, dv, lddv, dkv_batch_stride);
-        MEDP_LAUNCH_CHECK("medp_attn_small_bwd(few queries)");
-        return 0;
-    }
-    MEDP_CHECK_ARG(small_bwd_lds(p) <= 160 * 1024, "attn_small_bwd: Lk too large for LDS");
-    launch_small_bwd<false>(p, dout, lddo, dq, lddq, dk, lddk, dv, lddv, dkv_batch_stride, (hipStream_t)stream);
-    MEDP_LAUNCH_CHECK("medp_attn_small_bwd");
-    return 0;
+    return small_bwd(p, dout, lddo, dq, lddq, dk, lddk, dv, dkv_batch_stride, (hipStream_t)stream);
 }
 
 // ---- key-masked form (nn.MultiheadAttention's key_padding_mask; the trajectory probe's 7 queries over V x W window tokens) -------
@@ -602,23 +612,11 @@ extern "C" int medp_attn_small_masked_fwd(const float* q, int ldq, long long q_b
                                           long long kv_batch_stride, void* o, int ldo, int o_bf16, float* attn_avg, int B, int Lq,
                                           int Lk, int H, int dh, float scale, float dropout_p, unsigned seed, unsigned stream_id,
                                           void* stream, const unsigned char* key_mask, long long mask_batch_stride) {
-    SmallAttnParams p{q, k, v, ldq, ldkv, ldkv, q_batch_stride, kv_batch_stride, B, Lq, Lk, H, dh, scale, dropout_p, 1.0f / (1.0f - dropout_p), seed, stream_id, medp_rng_epoch_ptr(), key_mask, mask_batch_stride};
+    const SmallAttnParams p = make_params(q, ldq, q_batch_stride, k, v, ldkv, kv_batch_stride, B, Lq, Lk, H, dh, scale, dropout_p, seed, stream_id,
+                                          key_mask, mask_batch_stride);
     MEDP_TRY(check(p));
     MEDP_CHECK_ARG(o && key_mask && mask_batch_stride >= Lk, "attn_small_masked_fwd: null output / mask, or mask rows shorter than Lk");
-    hipStream_t st = (hipStream_t)stream;
-    launch_small_fwd<true>(p, o, ldo, o_bf16, nullptr, st);
-    MEDP_LAUNCH_CHECK("medp_attn_small_masked_fwd");
-    if (attn_avg) {
-        const int nper = (Lk + 63) / 64;
-        const dim3 grid(B, (Lq + 3) / 4);
-        if (nper <= 1) attn_small_avg_kernel<1><<<grid, 256, 0, st>>>(p, attn_avg);
-        else if (nper <= 2) attn_small_avg_kernel<2><<<grid, 256, 0, st>>>(p, attn_avg);
-        else if (nper <= 4) attn_small_avg_kernel<4><<<grid, 256, 0, st>>>(p, attn_avg);
-        else if (nper <= 8) attn_small_avg_kernel<8><<<grid, 256, 0, st>>>(p, attn_avg);
-        else attn_small_avg_kernel<MAXK_PER_LANE><<<grid, 256, 0, st>>>(p, attn_avg);
-        MEDP_LAUNCH_CHECK("medp_attn_small_masked_fwd(attn_avg)");
-    }
-    return 0;
+    return small_fwd(p, o, ldo, o_bf16, attn_avg, (hipStream_t)stream);
 }
 
 extern "C" int medp_attn_small_masked_bwd(const float* dout, int lddo, const float* q, int ldq, long long q_batch_stride, const float* k,
@@ -627,12 +625,10 @@ extern "C" int medp_attn_small_masked_bwd(const float* dout, int lddo, const flo
                                           float scale, float dropout_p, unsigned seed, unsigned stream_id, void* stream,
                                           const unsigned char* key_mask, long long mask_batch_stride) {
     (void)lddkv_unused;
-    SmallAttnParams p{q, k, v, ldq, ldkv, ldkv, q_batch_stride, kv_batch_stride, B, Lq, Lk, H, dh, scale, dropout_p, 1.0f / (1.0f - dropout_p), seed, stream_id, medp_rng_epoch_ptr(), key_mask, mask_batch_stride};
+    const SmallAttnParams p = make_params(q, ldq, q_batch_stride, k, v, ldkv, kv_batch_stride, B, Lq, Lk, H, dh, scale, dropout_p, seed, stream_id,
+                                          key_mask, mask_batch_stride);
     MEDP_TRY(check(p));
     MEDP_CHECK_ARG(dout && dq && dk && dv, "attn_small_masked_bwd: null gradient buffer");
     MEDP_CHECK_ARG(key_mask && mask_batch_stride >= Lk, "attn_small_masked_bwd: null mask, or mask rows shorter than Lk");
-    MEDP_CHECK_ARG(small_bwd_lds(p) <= 160 * 1024, "attn_small_masked_bwd: Lk too large for LDS");
-    launch_small_bwd<true>(p, dout, lddo, dq, lddq, dk, lddk, dv, lddk, dkv_batch_stride, (hipStream_t)stream);
-    MEDP_LAUNCH_CHECK("medp_attn_small_masked_bwd");
-    return 0;
+    return small_bwd(p, dout, lddo, dq, lddq, dk, lddk, dv, dkv_batch_stride, (hipStream_t)stream);
 }

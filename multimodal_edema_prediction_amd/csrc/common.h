@@ -46,6 +46,15 @@ void medp_set_error(const char* fmt, ...);
 // the tile.  hipcc emits this wait in front of __syncthreads() today (checked in the ISA, tools/isa_hazard_audit.py); it is
 // written out so that the guarantee does not hang on the compiler version.
 #define MEDP_WAIT_LDS_DMA() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+// one LDS-DMA piece: every lane hands over 16 bytes of global memory, the wave's 1 KiB lands at `lds_wave_base` in lane order
+__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+// transposing LDS read (ds_read_b64_tr_b16): 4 bf16 of this lane's MFMA operand column out of a row-major tile
+__device__ __forceinline__ bf16x4 lds_tr16(const char* addr) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(addr));
+}
 #define MEDP_TRY(expr)               \
     do {                             \
         int rc__ = (expr);           \

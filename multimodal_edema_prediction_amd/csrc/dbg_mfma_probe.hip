@@ -9,10 +9,6 @@
 namespace {
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
 
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc, (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
 template <int PIECES, int READS>
 __global__ __launch_bounds__(256) void mfma_dma_probe_kernel(const char* __restrict__ src, size_t src_bytes, int iters, unsigned long long* out, float* sink) {
     extern __shared__ __attribute__((aligned(16))) char smem[];          // 128 KiB

@@ -46,11 +46,6 @@ struct GemmParams {
     int nsplit;
 };
 
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 // TAG only gives the CXR-encoder launches their own kernel symbol, so a kernel trace separates the ViT GEMMs (the step's
 // dominant kernel, 4 shapes x 12 layers) from the DuETT / fusion-head launches of the same code.
 template <int BM, int BN, int TAG>

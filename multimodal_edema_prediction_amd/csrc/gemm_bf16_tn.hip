@@ -15,14 +15,6 @@ namespace {
 
 __device__ __attribute__((aligned(16))) uint32_t g_zero16_tn[4] = {0, 0, 0, 0};
 
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ bf16x4 lds_tr16(const char* addr) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(addr));
-}
-
 struct TnParams {
     const bf16_t* dY;   // [M, N] ld = lddy
     const bf16_t* X;    // [M, K] ld = ldx

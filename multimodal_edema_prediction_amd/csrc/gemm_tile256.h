@@ -39,11 +39,6 @@ namespace {
 
 __device__ __attribute__((aligned(16))) uint32_t g_zero16_t256[4] = {0, 0, 0, 0};   // source of every out-of-range 16-B chunk
 
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 constexpr int BN = 256, HALF = 128 * 128, KBUF = 4 * HALF;   // 16 KiB half-tile, 64 KiB K-tile buffer
 
 // patch write -> read (and read -> next write) inside ONE wave: the LDS executes a wave's operations in order, only the

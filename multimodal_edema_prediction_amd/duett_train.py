@@ -303,7 +303,7 @@ _MFMA_ATTN = __import__("os").environ.get("MEDP_DUETT_TRAIN_MFMA_ATTN", "1") == 
 
 class SelfAttnQKVFn(torch.autograd.Function):
     """qkv [B, N, 3*H*dh] (q | k | v column blocks) -> [B, N, H*dh]; dense softmax, dropout on the probabilities.
-    bf16 mode: the MFMA kernels of csrc/attention_dh16_train.hip (head dim <= 16, N <= 272); fp32 kernel mode or other shapes: the
+    bf16 mode: the MFMA kernels of csrc/attention_dh16.hip (head dim <= 16, N <= 272); fp32 kernel mode or other shapes: the
     fp32 VALU kernels of csrc/attention_small.hip.  Both draw the same dropout mask."""
 
     @staticmethod
@@ -314,13 +314,10 @@ class SelfAttnQKVFn(torch.autograd.Function):
         dh = D // H
         ctx.cfg = (H, p, seed, sid)
         if _MFMA_ATTN and Fn.precision() != "fp32":
-            o = torch.empty((B, N, D), dtype=torch.float32, device=qkv.device)
-            lse = torch.empty((B * H * N,), dtype=torch.float32, device=qkv.device)
-            rc = lib().medp_attn_dh16_train_fwd(ptr(qkv), D3, ptr(o), D, ptr(lse), 0, B, N, H, dh, dh ** -0.5, p, seed, sid, stream())
-            if rc != -2:
-                check(rc, "attn_dh16_train_fwd")
-                ctx.save_for_backward(qkv, lse)
-                return o
+            r = Fn.attn_dh16_train_fwd(qkv, B, N, H, dh, dropout_p=p, seed=seed, stream_id=sid)
+            if r is not None:
+                ctx.save_for_backward(qkv, r[1])
+                return r[0].view(B, N, D)
         o = Fn.attn_small_fwd(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], B, N, N, H, dh, dh ** -0.5, q_batch_stride=N * D3,
                               kv_batch_stride=N * D3, dropout_p=p, seed=seed, stream_id=sid)
         ctx.save_for_backward(qkv)
@@ -333,18 +330,13 @@ class SelfAttnQKVFn(torch.autograd.Function):
         B, N, D3 = qkv.shape
         D = D3 // 3
         dh = D // H
-        dqkv = torch.empty_like(qkv)
-        do2 = do.contiguous().view(B * N, D)
+        do = do.contiguous()
         if len(ctx.saved_tensors) == 2:                       # the forward ran on the matrix cores: so does the backward
-            lse = ctx.saved_tensors[1]
-            delta = torch.empty_like(lse)
-            check(lib().medp_attn_dh16_train_bwd(ptr(do2), D, ptr(qkv), D3, ptr(lse), ptr(delta), ptr(dqkv), D3, 0, B, N, H, dh, dh ** -0.5, p, seed,
-                                                 sid, stream()), "attn_dh16_train_bwd")
-            return dqkv, None, None, None, None
-        base = dqkv.data_ptr()
-        check(lib().medp_attn_small_bwd(ptr(do2), D, ptr(qkv), D3, N * D3, qkv.data_ptr() + 4 * D, qkv.data_ptr() + 8 * D, D3, N * D3, base, D3,
-                                        base + 4 * D, D3, base + 8 * D, 0, N * D3, B, N, N, H, dh, dh ** -0.5, p, seed, sid, stream()),
-              "attn_small_bwd(qkv)")
+            dqkv = Fn.attn_dh16_train_bwd(do, qkv, ctx.saved_tensors[1], B, N, H, dh, dropout_p=p, seed=seed, stream_id=sid)
+            return dqkv.view_as(qkv), None, None, None, None
+        dqkv = torch.empty_like(qkv)
+        Fn.attn_small_bwd(do, qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], B, N, N, H, dh, dh ** -0.5, q_batch_stride=N * D3,
+                          kv_batch_stride=N * D3, dropout_p=p, seed=seed, stream_id=sid, dq_out=dqkv[..., :D], dkv_out=dqkv[..., D:])
         return dqkv, None, None, None, None
 
 
@@ -368,7 +360,7 @@ def _scalenorm_bwd_join(dh, x, g, rn, d_pass):
 class AttnHalfFn(torch.autograd.Function):
     """x + to_out(Attention(ScaleNorm(x)))  — the attention half of an x_transformers pre-norm block (duett/duett.py:95-105) as ONE autograd
     node with 16-bit hand-overs inside: ScaleNorm writes the qkv GEMM's bf16 operand, that GEMM writes bf16 q | k | v, the MFMA attention
-    (csrc/attention_dh16_train.hip, io_bf16 = 1) reads them and writes bf16 o, the out-projection adds the residual in its epilogue.
+    (csrc/attention_dh16.hip, io_bf16 = 1) reads them and writes bf16 o, the out-projection adds the residual in its epilogue.
     Backward: one cast of dY, then dO, dQ | dK | dV in bf16 between the kernels, and the ScaleNorm backward joined with dY (the residual's
     gradient) in one out-of-place pass.
     Every value is rounded to bf16 exactly where the separate nodes (ScaleNormFn -> LinearFn -> SelfAttnQKVFn -> LinearFn) round it, so
@@ -383,10 +375,7 @@ class AttnHalfFn(torch.autograd.Function):
         dh = Dv // H
         h16, rn = Fn.scalenorm(xc, g, eps, out_dtype=BF16, save_rnorm=True)
         qkv16 = Fn.gemm(h16.view(B * N, D), A.weights_cat_bf16(ws), out_dtype=BF16, k=D)             # [B*N, 3 Dv]
-        o16 = torch.empty((B * N, Dv), dtype=BF16, device=x.device)
-        lse = torch.empty((B * H * N,), dtype=F32, device=x.device)
-        check(lib().medp_attn_dh16_train_fwd(ptr(qkv16), 3 * Dv, ptr(o16), Dv, ptr(lse), 1, B, N, H, dh, dh ** -0.5, p, seed, sid, stream()),
-              "attn_dh16_train_fwd(bf16)")
+        o16, lse = Fn.attn_dh16_train_fwd(qkv16, B, N, H, dh, dropout_p=p, seed=seed, stream_id=sid)     # (_fused_nodes_ok: the kernels take the shape)
         y = Fn.gemm(o16, A.weight_bf16(wo), residual=xc.view(B * N, D), out_dtype=F32, k=Dv)
         ctx.save_for_backward(xc, g, rn, h16, qkv16, lse, o16, wq, wk, wv, wo)
         ctx.cfg = (H, p, seed, sid)
@@ -404,10 +393,7 @@ class AttnHalfFn(torch.autograd.Function):
         dy16 = Fn.operand(dy2)
         do16 = Fn.gemm(dy16, A.weight_t_bf16(wo), out_dtype=BF16, k=D)                                # [B*N, Dv]
         dwo = Fn.gemm_tn(dy16, o16)
-        dqkv16 = torch.empty_like(qkv16)
-        delta = torch.empty_like(lse)
-        check(lib().medp_attn_dh16_train_bwd(ptr(do16), do16.stride(0), ptr(qkv16), 3 * Dv, ptr(lse), ptr(delta), ptr(dqkv16), 3 * Dv, 1, B, N, H,
-                                             dh, dh ** -0.5, p, seed, sid, stream()), "attn_dh16_train_bwd(bf16)")
+        dqkv16 = Fn.attn_dh16_train_bwd(do16, qkv16, lse, B, N, H, dh, dropout_p=p, seed=seed, stream_id=sid)
         dhid = Fn.gemm(dqkv16, A.weights_cat_t_bf16(ws), out_dtype=F32, k=3 * Dv)                     # [B*N, D]
         dwq, dwk, dwv = Fn.gemm_tn(dqkv16, h16.view(B * N, D)).split([w.shape[0] for w in ws], 0)
         dx, dg = _scalenorm_bwd_join(dhid, xc, g, rn, dy2)
@@ -462,7 +448,7 @@ def _fused_nodes_ok(m, x):
     dh = Dv // m.heads
     hid = ff[0][0].weight.shape[0]
     return (D % 8 == 0 and Dv % 8 == 0 and hid % 8 == 0 and a.to_out.bias is None and ff[0][0].bias is not None and ff[2].bias is not None
-            and lib().medp_attn_dh16_train_supported(B, N, m.heads, dh, 3 * Dv, Dv) == 1)
+            and Fn.attn_dh16_train_supported(B, N, m.heads, dh, 3 * Dv, Dv))
 
 
 # ------------------------------------------------------------------------------------------------ the composition

@@ -232,6 +232,61 @@ def attn_dh64_bwd(dout: torch.Tensor, qkv: torch.Tensor, o: torch.Tensor, lse: t
     return dqkv
 
 
+def attn_dh16_fwd(qkv: torch.Tensor, B: int, N: int, H: int, dh: int, *, o=None):
+    """Inference form of the MFMA attention for head dims <= 16: qkv fp32 [B*N, 3*H*dh] rows (q | k | v column blocks, ld = row stride) ->
+    o bf16 [B*N, H*dh] (`o`: a caller's buffer).  None when the shape is outside the kernel (the library's -2)."""
+    D = H * dh
+    q2 = qkv.reshape(B * N, qkv.shape[-1])
+    assert q2.dtype == F32
+    if o is None:
+        o = torch.empty((B * N, D), dtype=BF16, device=qkv.device)
+    rc = lib().medp_attn_dh16_fwd(ptr(q2), _ld(q2), ptr(o), _ld(o), B, N, H, dh, dh ** -0.5, stream())
+    if rc == -2:
+        return None
+    check(rc, "attn_dh16_fwd")
+    return o
+
+
+def attn_dh16_train_supported(B: int, N: int, H: int, dh: int, ld: int, ldo: int) -> bool:
+    """Whether the training-form kernels take the shape (qkv / o row strides ld / ldo; 16-byte aligned buffers assumed)."""
+    return lib().medp_attn_dh16_train_supported(B, N, H, dh, ld, ldo) == 1
+
+
+def attn_dh16_train_fwd(qkv: torch.Tensor, B: int, N: int, H: int, dh: int, *, dropout_p=0.0, seed=0, stream_id=0, o=None, lse=None):
+    """Training form: qkv [B*N, 3*H*dh] rows, fp32 or bf16 (the 16-bit hand-over form) -> (o [B*N, H*dh] of qkv's dtype, lse fp32 [B*H*N],
+    the log2-domain log-sum-exp the backward reads).  None when the shape is outside the kernels (the library's -2)."""
+    D = H * dh
+    q2 = qkv.reshape(B * N, qkv.shape[-1])
+    assert q2.dtype in (F32, BF16)
+    if o is None:
+        o = torch.empty((B * N, D), dtype=q2.dtype, device=qkv.device)
+    if lse is None:
+        lse = torch.empty((B * H * N,), dtype=F32, device=qkv.device)
+    assert o.dtype == q2.dtype and lse.dtype == F32
+    rc = lib().medp_attn_dh16_train_fwd(ptr(q2), _ld(q2), ptr(o), _ld(o), ptr(lse), int(q2.dtype == BF16), B, N, H, dh, dh ** -0.5,
+                                        dropout_p, seed, stream_id, stream())
+    if rc == -2:
+        return None
+    check(rc, "attn_dh16_train_fwd")
+    return o, lse
+
+
+def attn_dh16_train_bwd(dout: torch.Tensor, qkv: torch.Tensor, lse: torch.Tensor, B: int, N: int, H: int, dh: int, *, dropout_p=0.0, seed=0,
+                        stream_id=0, dqkv=None):
+    """Backward of `attn_dh16_train_fwd` (same dropout arguments): dout [B*N, H*dh] rows of qkv's dtype -> dqkv (dq | dk | dv column blocks,
+    qkv's shape and dtype; `dqkv`: a caller's buffer)."""
+    q2, d2 = qkv.reshape(B * N, qkv.shape[-1]), dout.reshape(B * N, H * dh)
+    assert d2.dtype == q2.dtype
+    if dqkv is None:
+        dqkv = torch.empty((B * N, 3 * H * dh), dtype=q2.dtype, device=qkv.device)
+    g2 = dqkv.view(B * N, dqkv.shape[-1])
+    assert g2.dtype == q2.dtype
+    delta = torch.empty_like(lse)
+    check(lib().medp_attn_dh16_train_bwd(ptr(d2), _ld(d2), ptr(q2), _ld(q2), ptr(lse), ptr(delta), ptr(g2), _ld(g2), int(q2.dtype == BF16), B, N, H,
+                                         dh, dh ** -0.5, dropout_p, seed, stream_id, stream()), "attn_dh16_train_bwd")
+    return dqkv
+
+
 def attn_small_fwd(q, k, v, B, Lq, Lk, H, dh, scale, *, q_batch_stride=None, kv_batch_stride=None, out_dtype=F32,
                    dropout_p=0.0, seed=0, stream_id=0, attn_avg=None, key_mask=None):
     """q fp32 rows [.., H*dh] (ld = q.stride(-2)); k, v fp32 with a common row stride.  `key_mask`: uint8 [B, Lk], non-zero =
@@ -256,20 +311,22 @@ def _key_mask_args(key_mask, B, Lk):
 
 
 def attn_small_bwd(dout, q, k, v, B, Lq, Lk, H, dh, scale, *, q_batch_stride=None, kv_batch_stride=None, dropout_p=0.0,
-                   seed=0, stream_id=0, dkv_out=None, key_mask=None):
+                   seed=0, stream_id=0, dkv_out=None, dq_out=None, key_mask=None):
     """Returns (dq [B,Lq,D], dk, dv).  dk/dv are the two column halves of one [B, Lk, 2D] buffer (`dkv_out`, which may be a
-    strided view, e.g. rows 1.. of a [B, Lk+1, 2D] tensor) so the fused K|V projection gets its gradient without a concat."""
+    strided view, e.g. rows 1.. of a [B, Lk+1, 2D] tensor) so the fused K|V projection gets its gradient without a concat.
+    `dq_out`: a [B, Lq, D] view whose batches abut (ld = its row stride), e.g. the q column block of a dq | dk | dv buffer."""
     ldq, ldkv = q.stride(-2), k.stride(-2)
     qbs = Lq * ldq if q_batch_stride is None else q_batch_stride
     kbs = Lk * ldkv if kv_batch_stride is None else kv_batch_stride
     D = H * dh
-    dq = torch.empty((B, Lq, D), dtype=F32, device=k.device)
+    dq = torch.empty((B, Lq, D), dtype=F32, device=k.device) if dq_out is None else dq_out
+    assert dq.shape == (B, Lq, D) and dq.stride(-1) == 1 and dq.stride(0) == Lq * dq.stride(1)      # the C ABI has no dq batch stride
     if dkv_out is None:
         dkv_out = torch.empty((B, Lk, 2 * D), dtype=F32, device=k.device)
     assert dkv_out.stride(-1) == 1 and dkv_out.shape[-1] == 2 * D
     d2 = dout.reshape(B * Lq, D)
     base = dkv_out.data_ptr()
-    args = (ptr(d2), _ld(d2), ptr(q), ldq, qbs, ptr(k), ptr(v), ldkv, kbs, ptr(dq), D, base, dkv_out.stride(-2), base + 4 * D, 0,
+    args = (ptr(d2), _ld(d2), ptr(q), ldq, qbs, ptr(k), ptr(v), ldkv, kbs, ptr(dq), dq.stride(1), base, dkv_out.stride(-2), base + 4 * D, 0,
             dkv_out.stride(0), B, Lq, Lk, H, dh, scale, dropout_p, seed, stream_id, stream())
     if key_mask is None:
         check(lib().medp_attn_small_bwd(*args), "attn_small_bwd")

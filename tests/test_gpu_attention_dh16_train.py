@@ -1,6 +1,7 @@
-"""DuETT's attention in training form on the matrix cores (csrc/attention_dh16_train.hip: 2 heads of dim 12 over 49 / 97 tokens,
+"""DuETT's attention in training form on the matrix cores (csrc/attention_dh16.hip: 2 heads of dim 12 over 49 / 97 tokens,
 dropout on the probabilities): forward and all three gradients against fp64 on the bf16-rounded operands, the dropout mask
-against the fp32 VALU kernels of attention_small.hip (same counter hash), and the autograd function the student path uses."""
+against the fp32 VALU kernels of attention_small.hip (same counter hash), the autograd function the student path uses, and the
+inference export of the same file, which is the same arithmetic."""
 import os
 import sys
 
@@ -110,3 +111,53 @@ def test_autograd_function_takes_the_mfma_path_and_matches_the_fp32_mode():
     assert float((o16 - o32).abs().max()) <= 1e-2 * float(o32.abs().max())
     assert float((g16 - g32).abs().max()) <= 3e-2 * float(g32.abs().max())
     assert not torch.equal(o16, o32)                                                                   # (two different kernels did run)
+
+
+def _inference(qkv, H, o=None):
+    from multimodal_edema_prediction_amd.abi import lib, ptr, stream
+    B, N, D3 = qkv.shape
+    D = D3 // 3
+    o = torch.full((B, N, D), float("nan"), device=DEV, dtype=torch.bfloat16) if o is None else o
+    return lib().medp_attn_dh16_fwd(ptr(qkv), D3, ptr(o), D, B, N, H, D // H, (D // H) ** -0.5, stream()), o
+
+
+# one shape per NT bucket edge (2 / 4 / 7 / 10 / 17 key tiles of 16) and the ragged ones
+@pytest.mark.parametrize("B,N,H,dh", [(1, 16, 1, 4), (3, 17, 2, 12), (2, 33, 2, 12), (2, 97, 2, 12), (1, 113, 1, 16), (1, 161, 3, 8), (1, 272, 1, 12)])
+def test_inference_export_has_the_bits_of_the_training_forward(B, N, H, dh):
+    """medp_attn_dh16_fwd (fp32 in, bf16 out) and medp_attn_dh16_train_fwd at p = 0 (fp32 in and out) are one arithmetic: the same MFMA chain,
+    the same exp2(fma) and the same ascending sum, so the bf16 output is the fp32 output rounded."""
+    torch.manual_seed(4)
+    qkv = (torch.randn(B, N, 3 * H * dh) * 0.8).to(DEV)
+    rc, o16 = _inference(qkv, H)
+    assert rc == 0
+    o32, _ = _call(qkv, torch.zeros(B, N, H * dh, device=DEV), H)
+    assert not torch.isnan(o16.float()).any()                                                          # every element written
+    assert torch.equal(o16, o32.to(torch.bfloat16))
+
+
+def test_shapes_outside_the_kernels_return_minus_two():
+    """Both forwards answer -2 (nothing launched: the caller takes attention_small.hip) to a head dim, a token count or a row stride they are not
+    built for.  An o that is only 8-byte aligned is enough for the inference form's 8-byte stores of bf16, not for the training form."""
+    from multimodal_edema_prediction_amd.abi import lib, ptr, stream
+
+    def both(B, N, H, dh, ld):
+        D = H * dh
+        qkv = torch.zeros(B * N, ld, device=DEV)
+        o16, o32, lse = torch.zeros(B * N, D, device=DEV, dtype=torch.bfloat16), torch.zeros(B * N, D, device=DEV), torch.zeros(B * H * N, device=DEV)
+        return (lib().medp_attn_dh16_fwd(ptr(qkv), ld, ptr(o16), D, B, N, H, dh, dh ** -0.5, stream()),
+                lib().medp_attn_dh16_train_fwd(ptr(qkv), ld, ptr(o32), D, ptr(lse), 0, B, N, H, dh, dh ** -0.5, 0.0, 0, 0, stream()))
+
+    assert both(1, 16, 1, 20, 60) == (-2, -2)                     # head dim 20
+    assert both(1, 273, 1, 4, 12) == (-2, -2)                     # N = 273
+    assert both(1, 16, 2, 12, 3 * 24 + 2) == (-2, -2)             # row stride 3 D + 2
+    assert both(1, 16, 2, 12, 3 * 24) == (0, 0)                   # (the same shape with the plain stride is taken)
+    torch.manual_seed(5)
+    B, N, H, dh = 1, 16, 2, 12
+    D = H * dh
+    qkv = (torch.randn(B, N, 3 * D) * 0.8).to(DEV)
+    rc, o_ref = _inference(qkv, H)
+    buf16 = torch.full((B * N * D + 4,), float("nan"), device=DEV, dtype=torch.bfloat16)
+    rc8, o8 = _inference(qkv, H, o=buf16[4:].view(B, N, D))       # 8 bytes past a 16-byte boundary
+    assert (rc, rc8) == (0, 0) and torch.equal(o8, o_ref) and torch.isnan(buf16[:4].float()).all()
+    buf32, lse = torch.zeros(B * N * D + 2, device=DEV), torch.zeros(B * H * N, device=DEV)
+    assert lib().medp_attn_dh16_train_fwd(ptr(qkv), 3 * D, ptr(buf32[2:]), D, ptr(lse), 0, B, N, H, dh, dh ** -0.5, 0.0, 0, 0, stream()) == -2

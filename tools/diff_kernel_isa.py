@@ -3,14 +3,18 @@
 ("the compiler emits the same instructions").  Needs hipcc, no GPU.
 
     python tools/diff_kernel_isa.py BASE [--work DIR] [--files a.hip ...] [--defines "" "MEDP_V7_PHASE_TRACE" ...] [--by-function]
+                                    [--merged NEW.hip=OLD1.hip,OLD2.hip ...]
 
 BASE is a git revision (its csrc/ and include/ are extracted to a temporary directory) or a directory holding a tree; the other side
 is the work tree (--work: another directory).  Every file is compiled for gfx950 at the flags of build.py with `-S --cuda-device-only`,
 once per -D set.  Default: every csrc/*.hip plain, plus gemm_bf16_v7.hip under each of its three build switches.  Dropped before the
 comparison: comments, .file / .ident / .loc lines, the per-translation-unit __hip_cuid_* symbol; the zero-chunk symbols (g_zero16*)
 are renamed to one name.  The resource-usage block of every kernel (.amdhsa_* lines) is part of the compared text.
-Prints IDENTICAL or the first differing hunk per file and -D set; with --by-function a differing file is also listed function by
-function (for a change that deliberately removes or edits one kernel of a file).  Exit status 1 on any difference."""
+Prints IDENTICAL, REORDERED (every function and kernel descriptor identical and the same lines around them, in another order: what a
+change of the host code's template instantiation order does) or the first differing hunk per file and -D set; with --by-function a differing file is also listed function by
+function (for a change that deliberately removes or edits one kernel of a file).  --merged: NEW.hip of the work tree took over the
+kernels of several files of BASE; those are compiled one by one and NEW.hip is listed function by function against their union.
+Exit status 1 on any difference."""
 import argparse
 import concurrent.futures
 import difflib
@@ -57,10 +61,13 @@ def normalise(text: str) -> list:
     return out
 
 
-def functions(lines: list) -> dict:
-    """name -> body, for every function (label ... .Lfunc_end) and every kernel descriptor (.amdhsa_kernel ... .end_amdhsa_kernel)"""
+def functions(lines: list, rest: list = None) -> dict:
+    """name -> body, for every function (label ... .Lfunc_end) and every kernel descriptor (.amdhsa_kernel ... .end_amdhsa_kernel);
+    the lines outside them are appended to `rest`"""
     fns, name, body = {}, None, []
     for i, line in enumerate(lines):
+        if name is None and rest is not None:
+            rest.append(re.sub(r"\.(LBB|Lfunc_end|Lfunc_begin)\d+", r".\1", line))
         m = re.match(r"^([A-Za-z_][\w.$]*):$", line)
         if name is None and m and i > 0 and "@function" in lines[i - 1]:
             name, body = m.group(1), []
@@ -94,29 +101,47 @@ def main() -> int:
     ap.add_argument("--files", nargs="*", help="sources under csrc/ (default: all *.hip)")
     ap.add_argument("--defines", nargs="*", help='-D sets, comma-separated names, "" for none (default: "" and, for gemm_bf16_v7.hip, its switches)')
     ap.add_argument("--by-function", action="store_true", help="list the functions of a differing file one by one")
+    ap.add_argument("--merged", nargs="*", default=[], metavar="NEW.hip=OLD1.hip,OLD2.hip", help="a work-tree file set against several files of the base")
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 1))
     args = ap.parse_args()
 
     with tempfile.TemporaryDirectory() as tmp:
         base = args.base if os.path.isdir(args.base) else extract(args.base, tmp)
         names = args.files or sorted(os.path.basename(f) for f in glob.glob(os.path.join(args.work, PKG, "csrc", "*.hip")))
+        merged = {new: olds.split(",") for new, olds in (m.split("=") for m in args.merged)}
         jobs = []
         for n in names:
             for d in (args.defines if args.defines is not None else [""] + (V7_DEFINES if n == "gemm_bf16_v7.hip" else [])):
                 jobs.append((n, d))
         with concurrent.futures.ThreadPoolExecutor(args.j) as pool:
-            futs = {(t, n, d): pool.submit(assembly, t, n, d) for n, d in jobs for t in (base, args.work)}
+            futs = {(t, n, d): pool.submit(assembly, t, n, d) for n, d in jobs for t in (base, args.work) if t == args.work or n not in merged}
+            futs.update({(base, o, ""): pool.submit(assembly, base, o, "") for olds in merged.values() for o in olds})
             differ = 0
             for n, d in jobs:
                 label = n + (f" [-D{d}]" if d else "")
+                if n in merged:
+                    fa = {k: v for o in merged[n] for k, v in functions(normalise(futs[(base, o, "")].result())).items()}
+                    fb = functions(normalise(futs[(args.work, n, d)].result()))
+                    states = {k: "only in base" if k not in fb else "only in work" if k not in fa else "identical" if fa[k] == fb[k] else "DIFFERENT"
+                              for k in sorted(set(fa) | set(fb))}
+                    same = sum(s == "identical" for s in states.values())
+                    differ += same != len(states)
+                    print(f"MERGED     {label} <- {' + '.join(merged[n])}  ({same} of {len(states)} functions identical)")
+                    for k, state in states.items():
+                        print(f"    {state:13s} {k}")
+                    continue
                 a, b = normalise(futs[(base, n, d)].result()), normalise(futs[(args.work, n, d)].result())
                 if a == b:
                     print(f"IDENTICAL  {label}  ({len(a)} lines)")
                     continue
+                ra, rb = [], []
+                fa, fb = functions(a, ra), functions(b, rb)
+                if fa == fb and sorted(ra) == sorted(rb):      # the templates were instantiated in another order: same code, another layout
+                    print(f"REORDERED  {label}  ({len(fa)} functions and descriptors identical, emitted in another order)")
+                    continue
                 differ += 1
                 print(f"DIFFERENT  {label}\n{first_hunk(a, b)}")
                 if args.by_function:
-                    fa, fb = functions(a), functions(b)
                     for k in sorted(set(fa) | set(fb)):
                         state = "only in base" if k not in fb else "only in work" if k not in fa else "identical" if fa[k] == fb[k] else "DIFFERENT"
                         print(f"    {state:13s} {k}")
