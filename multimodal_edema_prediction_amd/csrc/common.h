@@ -51,6 +51,18 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
+// The same piece through a BUFFER descriptor (`buffer_load_dwordx4 ... offen lds`): lane l hands over the 16 bytes at
+// base + voff(l) + soff.  The descriptor (four SGPRs: base, num_records in bytes) and `soff` are wave-uniform, `voff` is the only
+// per-lane operand — no 64-bit address per lane, and a lane whose voff is >= num_records reads nothing (it still counts in
+// vmcnt): the range check replaces the select of a zero source.  What such a lane leaves in LDS and which offsets the check
+// sees: tools/probe_buffer_lds.hip.
+typedef __amdgpu_buffer_rsrc_t medp_rsrc_t;
+__device__ __forceinline__ medp_rsrc_t lds_dma_rsrc(const void* base, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);   // raw buffer (stride 0), 32-bit data format
+}
+__device__ __forceinline__ void blds16(medp_rsrc_t rsrc, unsigned voff, unsigned soff, void* lds_wave_base) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, (int)voff, (int)soff, 0, 0);
+}
 // transposing LDS read (ds_read_b64_tr_b16): 4 bf16 of this lane's MFMA operand column out of a row-major tile
 __device__ __forceinline__ bf16x4 lds_tr16(const char* addr) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(addr));

@@ -647,3 +647,24 @@ extern "C" int medp_gemm_bf16_nt_ws(const void* A, const void* W, void* C, int M
     return medp_gemm_bf16_nt_tagged_ws(0, A, W, C, M, N, K, lda, ldw, ldc, bias, scale, residual, ldr, act, out_bf16, workspace,
                                        workspace_bytes, stream);
 }
+
+// Debug hook (NOT part of the C ABI in include/medp_hip.h; tests/test_gpu_gemm_buffer_dma.py): ONE launch of a 256-tile kernel on any
+// shape, past the grid-size rules of gemm_dispatch, so that a test reaches every staging path with a few tiles.  kernel 6: one tile
+// per workgroup (gemm_bf16_v6.hip; 224-row tiles where its own rule takes them), 7: persistent (gemm_bf16_v7.hip; with
+// medp_gemm_persistent_cap below the tile count the workgroups walk several tiles each).
+extern "C" int medp_dbg_gemm_tile256(int kernel, const void* A, const void* W, void* C, int M, int N, int K, int lda, int ldw, int ldc,
+                                     const float* bias, const float* scale, const float* residual, int ldr, int act, int out_bf16,
+                                     void* stream) {
+    MEDP_CHECK_ARG(kernel == 6 || kernel == 7, "gemm_tile256: kernel must be 6 or 7");
+    MEDP_CHECK_ARG(A && W && C && M > 0 && N > 0 && K > 0, "gemm_tile256: bad operand or shape");
+    MEDP_CHECK_ARG(K % 8 == 0 && lda % 8 == 0 && ldw % 8 == 0 && N % 4 == 0 && ldc % 4 == 0 && lda >= K && ldw >= K && ldc >= N &&
+                   (!residual || ldr % 4 == 0), "gemm_tile256: K, lda, ldw multiples of 8, N, ldc, ldr of 4, leading dimensions >= the row");
+    MEDP_CHECK_ARG(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)C & 15) == 0, "gemm_tile256: operands must be 16-byte aligned");
+    MEDP_CHECK_ARG(act == 0 || act == 1, "gemm_tile256: act must be 0 (none) or 1 (gelu)");
+    const MedpGemmArgs a{A, W, C, M, N, K, lda, ldw, ldc, bias, scale, residual, ldr, act, out_bf16, nullptr, 0};
+    if (kernel == 6) return medp_gemm_v6_launch(a, 0, stream);
+    MEDP_CHECK_ARG(medp_gemm_v7_supports(a), "gemm_tile256: the persistent kernel needs a bf16 result, no residual / scale, K %% 128 == 0, K >= 256");
+    const int rc = medp_gemm_v7_launch(a, 0, stream);
+    MEDP_CHECK_ARG(rc != -1, "gemm_tile256: no ticket block left");
+    return rc;
+}

@@ -17,7 +17,9 @@ static_assert(LDS_BYTES >= LDS_MAIN && LDS_BYTES <= 160 * 1024, "v6 LDS plan");
 // With GR = 112 the LDS layout, the DMA piece plan and therefore every vmcnt count stay those of GR = 128: a group's A half
 // still holds 128 rows, rows 112-127 are staged from the zero chunk, and the wave's last 16-row block (i = 3 of a = 1)
 // does no MFMA.  Every output element sees the same MFMAs in the same K order under either GR.
-template <int TAG, int GR>
+// BUF: the A / W stream goes through buffer descriptors (K % 64 == 0, see launch_v6_gr); without it every lane builds its
+// own address and selects the zero chunk for what lies past M, N or K.  Same pieces in the same order either way.
+template <int TAG, int GR, bool BUF>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmArgs p, unsigned* slot) {
     static_assert(GR == 128 || GR == 112, "v6 group rows");
     constexpr int BM = 2 * GR;
@@ -66,22 +68,43 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
     const int srow = tid >> 3, schunk = (tid & 7) ^ (srow & 7);       // source chunk for LDS position (tid & 7)
     const bf16_t* a_src[2][2];                                        // [half][piece] row base (k = 0) or nullptr
     const bf16_t* w_src[2][2];
+    // BUF: one descriptor in SGPRs per piece position (base = its first row, num_records = its rows below M / N in bytes: at most
+    // 64, 48 for rows 64-111 of a 112-row group, whose rows 112-127 nobody reads) and one byte offset per operand and lane, as
+    // in gemm_bf16_v7.hip; the K advance is the scalar offset.  (readfirstlane: see there.)
+    const unsigned voff_a = ((unsigned)srow * (unsigned)p.lda + (unsigned)(schunk * 8)) * 2u;
+    const unsigned voff_w = ((unsigned)srow * (unsigned)p.ldw + (unsigned)(schunk * 8)) * 2u;
+    medp_rsrc_t ra[2][2], rw[2][2];
+    const medp_rsrc_t none_rsrc = lds_dma_rsrc(A, 0);
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int ra = m0 + h * GR + j * 64 + srow, rw = n0 + h * 128 + j * 64 + srow;
-            a_src[h][j] = ((GR == 128 || j * 64 + srow < GR) && ra < p.M) ? A + (size_t)ra * p.lda + schunk * 8 : nullptr;
-            w_src[h][j] = rw < p.N ? W + (size_t)rw * p.ldw + schunk * 8 : nullptr;
+            if constexpr (BUF) {
+                const int ra0 = m0 + h * GR + j * 64, rw0 = n0 + h * 128 + j * 64;
+                const int na = min(j == 0 ? 64 : GR - 64, max(0, p.M - ra0)), nw = min(64, max(0, p.N - rw0));
+                ra[h][j] = lds_dma_rsrc(A + (size_t)ra0 * (size_t)p.lda, (unsigned)__builtin_amdgcn_readfirstlane(na * p.lda * 2));
+                rw[h][j] = lds_dma_rsrc(W + (size_t)rw0 * (size_t)p.ldw, (unsigned)__builtin_amdgcn_readfirstlane(nw * p.ldw * 2));
+            } else {
+                const int ra = m0 + h * GR + j * 64 + srow, rw = n0 + h * 128 + j * 64 + srow;
+                a_src[h][j] = ((GR == 128 || j * 64 + srow < GR) && ra < p.M) ? A + (size_t)ra * p.lda + schunk * 8 : nullptr;
+                w_src[h][j] = rw < p.N ? W + (size_t)rw * p.ldw + schunk * 8 : nullptr;
+            }
         }
     // piece j (rows 64 j .. 64 j + 63) of half-tile `which` (0: A rows 0-127, 1: A rows 128-255, 2: W rows 0-127, 3: W rows
-    // 128-255) of K-tile kt -> buffer kt & 1; past K (the tail of the stream) the source is the zero chunk, counts stay uniform
+    // 128-255) of K-tile kt -> buffer kt & 1; past K (the tail of the stream) the source is the zero chunk (BUF: a descriptor
+    // without records: nothing is read), counts stay uniform
     auto stage_piece = [&](int kt, int which, int j) {
         char* dst = piece_dst(smem, kt & 1, which, wave, j);
         const int k0 = kt * 64;
-        const bool kin = k0 + schunk * 8 < p.K;
-        const bf16_t* base = which < 2 ? a_src[which & 1][j] : w_src[which & 1][j];
-        glds16((base != nullptr && kin) ? base + k0 : zero, dst);
+        if constexpr (BUF) {
+            const bool past = kt >= nkt;
+            const medp_rsrc_t live = which < 2 ? ra[which & 1][j] : rw[which & 1][j];
+            blds16(past ? none_rsrc : live, which < 2 ? voff_a : voff_w, past ? 0u : (unsigned)k0 * 2u, dst);
+        } else {
+            const bool kin = k0 + schunk * 8 < p.K;
+            const bf16_t* base = which < 2 ? a_src[which & 1][j] : w_src[which & 1][j];
+            glds16((base != nullptr && kin) ? base + k0 : zero, dst);
+        }
     };
     auto stage_a = [&](int kt, int j) { stage_piece(kt, 0, j); stage_piece(kt, 1, j); };
     auto stage_w = [&](int kt, int h) { stage_piece(kt, 2 + h, 0); stage_piece(kt, 2 + h, 1); };
@@ -271,12 +294,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
     MEDP_PROF_LEAVE(p.prof, p.prof_flags);
 }
 
-template <int TAG, int GR>
-int launch_v6_gr(const MedpGemmArgs& a, hipStream_t stream) {
+template <int TAG, int GR, bool BUF>
+int launch_v6_buf(const MedpGemmArgs& a, hipStream_t stream) {
     constexpr int BM = 2 * GR;
     const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
     MEDP_ONCE_PER_DEVICE({
-        hipFuncSetAttribute((const void*)gemm_bf16_nt_v6_kernel<TAG, GR>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        hipFuncSetAttribute((const void*)gemm_bf16_nt_v6_kernel<TAG, GR, BUF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     });
     // MEDP_V6_TICKETS=1: one-round grids launch 256 workgroups that queue for the tiles (see the kernel).  OFF by default: the
     // hypothesis it tests — proj / fc2 run 30-40 % slower inside the step because workgroups start late on CUs still holding the
@@ -284,9 +307,17 @@ int launch_v6_gr(const MedpGemmArgs& a, hipStream_t stream) {
     // ticket costs 1.2 us): what the other branch takes from these GEMMs is cache and memory bandwidth, not CU slots.
     static const int tickets_on = [] { const char* e = getenv("MEDP_V6_TICKETS"); return e ? atoi(e) : 0; }();
     unsigned* slot = (tickets_on && tiles >= 64 && tiles < 256) ? medp_gemm_ticket_block(stream) : nullptr;
-    gemm_bf16_nt_v6_kernel<TAG, GR><<<slot ? 256 : tiles, 512, LDS_BYTES, stream>>>(a, slot);
+    gemm_bf16_nt_v6_kernel<TAG, GR, BUF><<<slot ? 256 : tiles, 512, LDS_BYTES, stream>>>(a, slot);
     MEDP_LAUNCH_CHECK("medp_gemm_bf16_nt(v6)");
     return 0;
+}
+
+// The buffer-descriptor stream needs whole K-tiles (no chunk past K inside a K-tile: only the per-lane path can zero those) and
+// 64 rows of a piece within a descriptor's 32-bit num_records; everything else keeps the per-lane addresses.
+template <int TAG, int GR>
+int launch_v6_gr(const MedpGemmArgs& a, hipStream_t stream) {
+    const bool buf = a.K % 64 == 0 && a.lda < (1 << 24) && a.ldw < (1 << 24);
+    return buf ? launch_v6_buf<TAG, GR, true>(a, stream) : launch_v6_buf<TAG, GR, false>(a, stream);
 }
 
 // 224 x 256 tiles (GR = 112) for N = 768 where 256 x 256 tiles leave part of the chip idle: proj / fc2 at M = 64 x 257 are

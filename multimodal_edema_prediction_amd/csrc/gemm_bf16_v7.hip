@@ -81,16 +81,32 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v7_kernel(const MedpGemmA
 
     // ---- LDS-DMA staging: half-tile = 128 rows x 8 chunks; lane's two pieces are rows (tid>>3) and (tid>>3)+64 ------
     const int srow = tid >> 3, schunk = (tid & 7) ^ (srow & 7);       // source chunk for LDS position (tid & 7)
-    // Source state: the tile origin the A / W stream currently reads from (scalars, switched to the next tile near the end of
-    // a K-loop; NOBODY = past M / N: zero source) and ONE 32-bit element offset per operand for this lane's first piece —
-    // eight row pointers in VGPRs did not fit next to 128 accumulators once the epilogue sits inside the tile loop.
-    // The other pieces are scalar multiples of 64 rows away.  Host checks M*lda, N*ldw < 2^31.
-    const int NOBODY = 0x3fffff00;
-    int m_src, n_src;
-    unsigned a_off, w_off;
-    const unsigned lda64 = 64u * (unsigned)p.lda, ldw64 = 64u * (unsigned)p.ldw;
-    auto set_m = [&](int mm) { m_src = mm; a_off = (unsigned)(mm + srow) * (unsigned)p.lda + (unsigned)(schunk * 8); };
-    auto set_n = [&](int nn) { n_src = nn; w_off = (unsigned)(nn + srow) * (unsigned)p.ldw + (unsigned)(schunk * 8); };
+    // Source state: EIGHT buffer descriptors in SGPRs, one per 64-row piece position of the tile the A / W stream currently reads
+    // from (A rows 0-63 .. 192-255, W rows 0-63 .. 192-255: base = the position's first row, num_records = its rows below M / N,
+    // at most 64, in bytes), rebuilt with scalar operations where the stream switches to the next tile near the end of a K-loop
+    // (nobody, i.e. no next tile: no records), and ONE loop-invariant byte offset per operand and lane; the K advance is the
+    // instruction's scalar offset.  A load section therefore holds no address arithmetic on the vector ALU (it used to build a
+    // 64-bit address and select the zero chunk per piece, ~15 VALU per section, issued beside the partner wave's prioritised
+    // MFMAs), and rows past M / N are dropped by the range check: gemm_tile256.h says why whatever LDS then holds is harmless.
+    const unsigned voff_a = ((unsigned)srow * (unsigned)p.lda + (unsigned)(schunk * 8)) * 2u;
+    const unsigned voff_w = ((unsigned)srow * (unsigned)p.ldw + (unsigned)(schunk * 8)) * 2u;
+    medp_rsrc_t ra[4], rw[4];
+    // (readfirstlane: the clamp of a wave-uniform value is still selected as one vector instruction (v_med3), and a descriptor word
+    //  in a VGPR wraps every load that uses it in a loop over its distinct values)
+    auto set_m = [&](int mm) {         // mm < 0: nobody
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int rows = mm < 0 ? 0 : min(64, max(0, p.M - mm - q * 64));
+            ra[q] = lds_dma_rsrc(A + (size_t)(mm < 0 ? 0 : mm + q * 64) * (size_t)p.lda, (unsigned)__builtin_amdgcn_readfirstlane(rows * p.lda * 2));
+        }
+    };
+    auto set_n = [&](int nn) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int rows = nn < 0 ? 0 : min(64, max(0, p.N - nn - q * 64));
+            rw[q] = lds_dma_rsrc(W + (size_t)(nn < 0 ? 0 : nn + q * 64) * (size_t)p.ldw, (unsigned)__builtin_amdgcn_readfirstlane(rows * p.ldw * 2));
+        }
+    };
     set_m(m0);
     set_n(n0);
 #ifdef MEDP_V7_ABLATE_LOADS
@@ -103,12 +119,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v7_kernel(const MedpGemmA
         if (ablate_on) return;
 #endif
         char* dst = piece_dst(smem, b, which, wave, j);
-        const bool kin = k0 + schunk * 8 < p.K;
-        const int r = (which < 2 ? m_src : n_src) + (which & 1) * 128 + j * 64 + srow;
-        const bool ok = kin && r < (which < 2 ? p.M : p.N);
-        const unsigned off = (which < 2 ? a_off + ((which & 1) * 2 + j) * lda64 : w_off + ((which & 1) * 2 + j) * ldw64) + (unsigned)k0;
-        const bf16_t* live = (which < 2 ? A : W) + off;
-        glds16(ok ? live : zero, dst);
+        const int q = (which & 1) * 2 + j;
+        if (which < 2) blds16(ra[q], voff_a, (unsigned)k0 * 2u, dst);      // (K % 128 == 0: no chunk lies past K)
+        else blds16(rw[q], voff_w, (unsigned)k0 * 2u, dst);
     };
     auto stage_a = [&](int k0, int b, int j) { stage_piece(k0, b, 0, j); stage_piece(k0, b, 1, j); };
     auto stage_w = [&](int k0, int b, int h) { stage_piece(k0, b, 2 + h, 0); stage_piece(k0, b, 2 + h, 1); };
@@ -262,15 +275,15 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v7_kernel(const MedpGemmA
 #endif
         int t_next = -1, m0n = 0, n0n = 0;
         // The K-tile body is the shared one (gemm_tile256.h).  The stream runs two K-tiles ahead and from K-tile nkt-2 on belongs
-        // to the NEXT tile (its K-tiles 0 and 1; nobody: zero source): when the loop ends all of them but the last A piece are
+        // to the NEXT tile (its K-tiles 0 and 1; nobody: descriptors without records): when the loop ends all of them but the last A piece are
         // issued, and the W0 fragments of the next K-tile 0 are in registers.  Tiles start with those landed, so the waits of
         // K-tile 0 are skipped: the first wait that covers the previous tile's output stores is P2 of K-tile 1.
         auto before_p2 = [&](int kt) {
             if (kt == nkt - 2) {       // from here on the stream reads the next tile (P1 still staged this tile's last A piece)
                 t_next = __builtin_amdgcn_readfirstlane(mailbox[0]);
                 if (t_next >= 0) map.origin(t_next, MB, SN, BM, m0n, n0n);
-                set_m(t_next >= 0 ? m0n : NOBODY);
-                set_n(t_next >= 0 ? n0n : NOBODY);
+                set_m(t_next >= 0 ? m0n : -1);
+                set_n(t_next >= 0 ? n0n : -1);
             }
         };
         auto clock = [&](int k) { PT(k); };
@@ -450,10 +463,15 @@ int launch_v7(const MedpGemmArgs& a, hipStream_t stream) {
 
 }  // namespace
 
+bool medp_gemm_v7_supports(const MedpGemmArgs& a) {
+    return a.out_bf16 && a.residual == nullptr && a.scale == nullptr && a.N % 8 == 0 && a.ldc % 8 == 0 &&
+           a.K % 128 == 0 && a.K >= 256 && (long long)a.M * a.lda < (1ll << 31) && (long long)a.N * a.ldw < (1ll << 31) &&
+           a.lda < (1 << 24) && a.ldw < (1 << 24);       // (64 rows of a piece within a descriptor's 32-bit num_records)
+}
+
 bool medp_gemm_v7_eligible(const MedpGemmArgs& a) {
     const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    return tiles > NWG && a.out_bf16 && a.residual == nullptr && a.scale == nullptr && a.N % 8 == 0 && a.ldc % 8 == 0 &&
-           a.K % 128 == 0 && a.K >= 256 && (long long)a.M * a.lda < (1ll << 31) && (long long)a.N * a.ldw < (1ll << 31);
+    return tiles > NWG && medp_gemm_v7_supports(a);
 }
 
 // returns -1 when no private ticket block is left (caller launches v6 instead)
