@@ -15,8 +15,6 @@
 // "full block" vs "ragged tail"; the softmax is max / fma / v_exp_f32 / add per score (scale folded into the fma, bare
 // hardware exp2, scalar f32 ops — see key_block), and the 4-lane max butterfly uses v_permlane16/32_swap (VALU) instead
 // of ds_bpermute round trips.
-#include <stdlib.h>
-
 #include "common.h"
 #include "medp_hip.h"
 
@@ -513,7 +511,7 @@ static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
     AttnParams p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, B, S, H, ldq, ldk, ldv, ldo,
                  scale * 1.4426950408889634f, 0, lse};
     // S = 257 (224 x 224 images): the one-workgroup-per-(batch, head) kernel (MEDP_ATTN_S257=0: the general kernel, for A/B runs)
-    static const int s257_on = [] { const char* e = getenv("MEDP_ATTN_S257"); return e ? atoi(e) : 1; }();
+    static const int s257_on = medp_env_int("MEDP_ATTN_S257", 1);
     if (S == S257 && s257_on) {
         MEDP_ONCE_PER_DEVICE({
             hipFuncSetAttribute((const void*)attn_fwd_dh64_s257_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_257);
@@ -525,7 +523,7 @@ static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
         const int slots = g_s257_slots_override > 0 ? g_s257_slots_override : dev_slots;
         // Measured (B 64, H 12: 768 (b, h) on 512 slots): whole units only 32.2 us, whole + half units 37.8 us — a (b, h)'s cost is its 99 KB of
         // loads, not its 16 subtiles of arithmetic, and a half unit loads all of K / V for half the queries.  Default: whole units.
-        static const int bal = [] { const char* e = getenv("MEDP_ATTN_S257_BALANCE"); return e ? atoi(e) : 0; }();
+        static const int bal = medp_env_int("MEDP_ATTN_S257_BALANCE", 0);
         const int n = B * H, rem = n % slots;
         const bool halves = bal || g_s257_slots_override > 0;        // (the test hook plans halves on its pretended slots)
         const int n_half = (halves && n > slots && rem > 0 && 2 * rem <= slots) ? rem : 0, n_whole = n - n_half;
@@ -541,7 +539,7 @@ static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
         hipFuncSetAttribute((const void*)attn_fwd_dh64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     });
     const int ntile = (S + 15) / 16;
-    static const int w8_min_s = [] { const char* e = getenv("MEDP_ATTN_W8_MIN_S"); return e ? atoi(e) : 512; }();      // 0 / huge: never (A/B runs)
+    static const int w8_min_s = medp_env_int("MEDP_ATTN_W8_MIN_S", 512);      // 0 / huge: never (A/B runs)
     if (w8_min_s > 0 && S >= w8_min_s) {
         MEDP_ONCE_PER_DEVICE({
             hipFuncSetAttribute((const void*)attn_fwd_dh64_w8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);

@@ -8,8 +8,6 @@
 // reductions), head-dim on lanes for PV.  Backward recomputes the probabilities, writes dQ per query and
 // accumulates dK/dV in the block's own (batch, head) slice — no cross-block atomics, bitwise reproducible.
 // Dropout on the probabilities uses the counter hash of common.h, regenerated in backward.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "attention_fq.h"
@@ -488,7 +486,7 @@ __global__ __launch_bounds__(FQ_T) void attn_fq_bwd_kernel(const SmallAttnParams
 
 // shapes the few-query kernels take: <= 8 queries, head dim 64, <= 1024 keys, 16-B aligned rows
 bool fq_eligible(const SmallAttnParams& p, const void* a, const void* b2, int lda, int ldb) {
-    static const int on = [] { const char* e = getenv("MEDP_ATTN_FEWQ"); return e ? atoi(e) : 1; }();
+    static const int on = medp_env_int("MEDP_ATTN_FEWQ", 1);
     return on && p.Lq <= FQ && p.dh == 64 && p.Lk <= FQ_MAXCH * FQ_T && ((p.ldk | p.ldv | lda | ldb) & 3) == 0 && (p.kv_bs & 3) == 0 &&
            ((((uintptr_t)p.k | (uintptr_t)p.v | (uintptr_t)a | (uintptr_t)b2) & 15) == 0);
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include <mutex>
 
@@ -73,10 +74,11 @@ __device__ __forceinline__ bf16x4 lds_tr16(const char* addr) {
         if (rc__ != 0) return rc__;  \
     } while (0)
 
-// internal (not part of the C ABI): GEMM launcher with a kernel-symbol tag; tag 1 = CXR-encoder block GEMMs
-int medp_gemm_bf16_nt_tagged(int tag, const void* A, const void* W, void* C, int M, int N, int K, int lda, int ldw, int ldc,
-                             const float* bias, const float* scale, const float* residual, int ldr, int act, int out_bf16,
-                             void* stream);
+// integer environment switch, `dflt` when unset; call sites keep it in a `static const`, so a switch is read once, at first use
+inline int medp_env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 // device pointer (may be null) to a uint32 "RNG epoch" mixed into every dropout seed: lets a captured HIP graph draw a
 // fresh mask on every replay although the per-call seeds are baked into the graph (set by medp_rng_set_epoch_ptr)

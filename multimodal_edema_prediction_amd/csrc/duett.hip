@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256) void time_embed_mfma_kernel(const float* __res
 // MEDP_EMBED_MFMA=0 (or medp_dbg_embed_mfma(0), tests): the VALU forms of the two embedding kernels, for A/B runs and bit comparisons
 int g_embed_mfma = -1;
 static int embed_mfma_on() {
-    if (g_embed_mfma < 0) { const char* e = getenv("MEDP_EMBED_MFMA"); g_embed_mfma = e ? (atoi(e) != 0) : 1; }
+    if (g_embed_mfma < 0) g_embed_mfma = medp_env_int("MEDP_EMBED_MFMA", 1) != 0;
     return g_embed_mfma;
 }
 
@@ -581,7 +581,7 @@ int launch_psi_embed_event(const MedpDuettWeights* w, const float* xs_static, co
     MEDP_CHECK_ARG(w->d_hidden_tab <= 256 && w->n_obs_rows >= 1 && w->n_obs_rows <= 64, "duett: tab encoder hidden size above 256 / n_obs table above 64 rows");
     // rows (= cells per lane) per workgroup.  Measured at cfg3 (tools/time_embed_variants.py): 1 -> 44 us, 2 -> 53 us, 4 -> 77 us:
     // fewer, longer waves lose more than the amortised weight reads win; 1 is the default.
-    static const int nb = [] { const char* e = getenv("MEDP_PSI_NB"); return e ? atoi(e) : 1; }();
+    static const int nb = medp_env_int("MEDP_PSI_NB", 1);
     int rc = nb >= 4 ? launch_psi_embed_event_nb<4>(w, xs_static, xs_ts, xe, h, psi0_out, B, T, s)
            : nb >= 2 ? launch_psi_embed_event_nb<2>(w, xs_static, xs_ts, xe, h, psi0_out, B, T, s) : -2;
     if (rc == -2) rc = launch_psi_embed_event_nb<1>(w, xs_static, xs_ts, xe, h, psi0_out, B, T, s);   // long rows: one per workgroup
@@ -635,7 +635,7 @@ int encoder_forward(const MedpEncoderWeights& e, const MedpDuettWeights* w, floa
         MEDP_TRY(medp_scalenorm_fwd(x, D, e.g_attn, h, D, 1, nullptr, M, D, w->norm_eps, stream));
     MEDP_TRY(medp_gemm_bf16_nt_ws(h, e.qkv_w, qkv, M, 3 * E, D, D, D, 3 * E, nullptr, nullptr, nullptr, 0, 0, 0, sp, ws.split_bytes, stream));
     // both axes' attention on the matrix cores (attention_dh16.hip); shapes it is not built for take the fp32 VALU kernel
-    static const bool mfma_attn = [] { const char* e2 = getenv("MEDP_DUETT_MFMA_ATTN"); return !e2 || atoi(e2) != 0; }();
+    static const bool mfma_attn = medp_env_int("MEDP_DUETT_MFMA_ATTN", 1) != 0;
     int arc = mfma_attn ? medp_attn_dh16_fwd(qkv, 3 * E, o, E, B, N, H, dh, 1.0f / sqrtf((float)dh), stream) : -2;
     if (arc == -2)
         arc = medp_attn_small_fwd(qkv, 3 * E, (long long)N * 3 * E, qkv + E, qkv + 2 * E, 3 * E, (long long)N * 3 * E, o, E, 1, nullptr, B, N,
@@ -680,7 +680,7 @@ extern "C" int medp_duett_encode(const MedpDuettWeights* w, const float* xs_stat
     MEDP_CHECK_ARG((size_t)B * T1 * V1 * E4 < (1ull << 31), "duett_encode: B*(T+1)*(V+1)*E/4 must stay below 2^31");
     // Layer 0, event view, in ONE launch: psi build + axis swap + event embedding + the event encoder's first ScaleNorm.
     // MEDP_DUETT_FUSED=0 keeps the separate launches (psi_embed -> swap -> scalenorm ...) for A/B runs; same values.
-    static const bool fused = [] { const char* e = getenv("MEDP_DUETT_FUSED"); return !e || atoi(e) != 0; }();
+    static const bool fused = medp_env_int("MEDP_DUETT_FUSED", 1) != 0;
     const int swap_grid = grid_for((size_t)B * T1 * V1 * E4);
     if (fused) {
         MEDP_TRY(launch_psi_embed_event(w, xs_static, xs_ts, xe, base + ws.h, psi0_out, B, T, s));

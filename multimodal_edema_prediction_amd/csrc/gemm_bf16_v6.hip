@@ -1,8 +1,7 @@
 // v6: the 256 x 256 x 64 ping-pong K-loop of gemm_tile256.h (tile map, phase plan and counted waits are described there), ONE tile
 // per workgroup, for every epilogue: bias / GELU / LayerScale / fp32 residual, fp32 or bf16 result, both sides of the LayerNorm fold.
-#include <stdlib.h>
-
 #include "common.h"
+#include "gemm_epilogue.h"
 #include "gemm_tile256.h"
 #include "gemm_variants.h"
 
@@ -234,19 +233,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
                 } else {
                     v += bias4;
                 }
-                if (p.act == 1) v = p.out_bf16 ? gelu_bf16_4(v) : gelu_erf4(v);
-                v *= scale4;
+                v = gemm_act_scale<true>(v, scale4, p.act, p.out_bf16);
                 if (has_res) v += res[half][it];
-                if (p.out_bf16) {
-                    uint2 o;
-                    o.x = pack_bf2(v[0], v[1]);
-                    o.y = pack_bf2(v[2], v[3]);
-                    typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-                    // non-temporal: the tile is written once and all 256 workgroups flush together (-2 % step time measured)
-                    __builtin_nontemporal_store((u32x2){o.x, o.y}, (u32x2*)((bf16_t*)p.C + (size_t)m * p.ldc + n));
-                } else {
-                    __builtin_nontemporal_store(v, (f32x4*)((float*)p.C + (size_t)m * p.ldc + n));
-                }
+                gemm_store4<true>(p.C, p.ldc, p.out_bf16, m, n, v);      // non-temporal
                 if (producer) {
                     uint2 o;
                     o.x = pack_bf2(v[0], v[1]);
@@ -305,7 +294,7 @@ int launch_v6_buf(const MedpGemmArgs& a, hipStream_t stream) {
     // hypothesis it tests — proj / fc2 run 30-40 % slower inside the step because workgroups start late on CUs still holding the
     // other branch's short kernels — did not hold (in-box A/B: proj 41.9 us static, 44.2 us queued; step 5.03 vs 5.12 ms; alone the
     // ticket costs 1.2 us): what the other branch takes from these GEMMs is cache and memory bandwidth, not CU slots.
-    static const int tickets_on = [] { const char* e = getenv("MEDP_V6_TICKETS"); return e ? atoi(e) : 0; }();
+    static const int tickets_on = medp_env_int("MEDP_V6_TICKETS", 0);
     unsigned* slot = (tickets_on && tiles >= 64 && tiles < 256) ? medp_gemm_ticket_block(stream) : nullptr;
     gemm_bf16_nt_v6_kernel<TAG, GR, BUF><<<slot ? 256 : tiles, 512, LDS_BYTES, stream>>>(a, slot);
     MEDP_LAUNCH_CHECK("medp_gemm_bf16_nt(v6)");
@@ -324,7 +313,7 @@ int launch_v6_gr(const MedpGemmArgs& a, hipStream_t stream) {
 // 65 x 3 = 195 tiles of 256 rows on 256 CUs, 74 x 3 = 222 of 224 rows.  Taken for the launches with a residual (proj / fc2)
 // and no LayerNorm fold.  MEDP_V6_N768=0: always 256 x 256 (A/B runs); 2: also the N = 768 launches without a residual.
 bool v6_use_224(const MedpGemmArgs& a) {
-    static const int mode = [] { const char* e = getenv("MEDP_V6_N768"); return e ? atoi(e) : 1; }();
+    static const int mode = medp_env_int("MEDP_V6_N768", 1);
     const int tiles256 = ((a.M + 255) / 256) * ((a.N + 255) / 256);
     const int tiles224 = ((a.M + 223) / 224) * ((a.N + 255) / 256);
     return mode != 0 && a.N == 768 && (a.residual != nullptr || mode == 2) && a.fold.c2 == nullptr && a.fold.stats_in == nullptr &&

@@ -17,7 +17,6 @@
 // the hardware dispatcher would have sent to that XCD in v6, so the band x super-column L2 locality of the v6 map holds.
 // A workgroup that draws a ticket past the end leaves; the last one to leave zeroes the tickets for the next launch.
 // The ticket block is private to one launch (host side: a ring for eager launches, never-reused slots under stream capture).
-#include <stdlib.h>
 #include <string.h>
 
 #include <atomic>
@@ -439,12 +438,12 @@ int launch_v7(const MedpGemmArgs& a, hipStream_t stream) {
     // tiles) and fc1 (780) need 3 and 4 rounds on 256 CUs and equally on 200; the 56 CUs left alone serve the other branches of
     // the step for the whole launch (teacher step 5.39 -> 5.19 ms, and the GEMMs themselves run 4 % faster: fewer L2 clients).
     // MEDP_V7_WGS (a multiple of 8, <= 256) caps the count: the rounds are then counted against the cap.
-    static const int env_cap = [] { const char* e = getenv("MEDP_V7_WGS"); const int v = e ? atoi(e) : NWG; return (v >= 8 && v <= NWG) ? (v & ~7) : NWG; }();
+    static const int env_cap = [] { const int v = medp_env_int("MEDP_V7_WGS", NWG); return (v >= 8 && v <= NWG) ? (v & ~7) : NWG; }();
     const int api_cap = g_api_cap.load();
     const int cap = api_cap > 0 ? api_cap : env_cap;
     const int ntiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
     const int rounds = (ntiles + cap - 1) / cap;
-    static const int fewest = [] { const char* e = getenv("MEDP_V7_FEWEST_WGS"); return e ? atoi(e) : 1; }();      // 0: always `cap` workgroups (A/B)
+    static const int fewest = medp_env_int("MEDP_V7_FEWEST_WGS", 1);      // 0: always `cap` workgroups (A/B)
     const int nwg = fewest ? min(cap, ((ntiles + rounds - 1) / rounds + 7) & ~7) : cap;
     // Tile walk inside an XCD: blocks of MB row-tiles x SN column-tiles (8 x 4 = one round of an XCD's 32 CUs; MEDP_V7_BLOCK=MBxSN
     // overrides).  Measured (FETCH_SIZE per launch, mean of qkv / fc1; in-box step time): 256 workgroups 8x4: 51.1 k KiB, 5.26 ms;
@@ -452,7 +451,7 @@ int launch_v7(const MedpGemmArgs& a, hipStream_t stream) {
     // re-fetch panels); 200 with 5x5: 71.1 k, same time; 192 workgroups 8x3 + the ragged rows as their own launch (every round
     // exactly one block): 48.0 k but 5.25 ms.  HBM traffic is not what binds these GEMMs (142.5 MB algorithmic = 18 us at 8 TB/s
     // against 65-100 us): the fastest arrangement is kept, the extra re-fetch is reported (profiles/traffic.json).
-    static const int env_mb = [] { const char* e = getenv("MEDP_V7_BLOCK"); return e ? atoi(e) : 0; }();
+    static const int env_mb = medp_env_int("MEDP_V7_BLOCK", 0);
     static const int env_sn = [] { const char* e = getenv("MEDP_V7_BLOCK"); const char* x = e ? strchr(e, 'x') : nullptr; return x ? atoi(x + 1) : 0; }();
     int mb = 8, sn = 4;
     if (env_mb > 0 && env_sn > 0) { mb = env_mb; sn = env_sn; }

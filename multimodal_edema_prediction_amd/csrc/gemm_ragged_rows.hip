@@ -9,6 +9,7 @@
 // accumulator) and the same epilogue arithmetic as gemm_bf16_v6.hip / gemm_bf16_v7.hip — so a row computes to the same bits
 // whichever kernel owns it (tests/test_gpu_gemm_persistent.py).
 #include "common.h"
+#include "gemm_epilogue.h"
 #include "gemm_variants.h"
 
 namespace {
@@ -45,16 +46,9 @@ __global__ __launch_bounds__(512) void gemm_ragged_rows_kernel(const MedpGemmArg
     if (a_ok && n < p.N) {                                  // host: N % 4 == 0
         const f32x4 bias4 = p.bias ? *(const f32x4*)(p.bias + n) : (f32x4){0.f, 0.f, 0.f, 0.f};
         const f32x4 scale4 = p.scale ? *(const f32x4*)(p.scale + n) : (f32x4){1.f, 1.f, 1.f, 1.f};
-        f32x4 v = acc + bias4;                              // (unconditional, as in the tile kernels: -0 + 0 = +0)
-        if (p.act == 1) v = p.out_bf16 ? gelu_bf16_4(v) : gelu_erf4(v);
-        v *= scale4;
+        f32x4 v = gemm_epi_preloaded<true>(acc, bias4, scale4, p.act, p.out_bf16);    // (unconditional bias, as in the tile kernels: -0 + 0 = +0)
         if (p.residual) v += *(const f32x4*)(p.residual + (size_t)m * p.ldr + n);
-        if (p.out_bf16) {
-            typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-            *(u32x2*)((bf16_t*)p.C + (size_t)m * p.ldc + n) = (u32x2){pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
-        } else {
-            *(f32x4*)((float*)p.C + (size_t)m * p.ldc + n) = v;
-        }
+        gemm_store4(p.C, p.ldc, p.out_bf16, m, n, v);
     }
     MEDP_PROF_LEAVE(p.prof, p.prof_flags);
 }

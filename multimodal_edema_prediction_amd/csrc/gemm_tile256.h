@@ -82,7 +82,7 @@ constexpr int BN = 256, HALF = 128 * 128, KBUF = 4 * HALF;   // 16 KiB half-tile
 
 // Tile index -> origin.  Workgroups are dispatched in index order, block b to XCD b % 8, one per CU (32 CUs per XCD).  The
 // FULL row-tiles come first: XCD x gets a contiguous run of them, walked in bands of MB row-tiles x super-columns of SN
-// column-tiles (see v3 in gemm_bf16.hip), so its L2 sees few panels; the cheap tiles of a ragged last row (M = 64 * 257: 64 live
+// column-tiles (see v3 in gemm_bf16_tiles.hip), so its L2 sees few panels; the cheap tiles of a ragged last row (M = 64 * 257: 64 live
 // rows, three quarters of their MFMAs skipped) take the highest indices, i.e. they are dispatched LAST.  fc1 (768 full + 12
 // ragged tiles) is then 96 full tiles = exactly 3 rounds per XCD plus a short ragged tail, instead of a fourth round that
 // holds one full tile per XCD.

@@ -17,8 +17,6 @@
 // their launch gaps — a gain of ~10 us per block; INSIDE the step the same epilogues cost +38 us per block (the side branch competes
 // for exactly the VALU / HBM time they add) and the step is 0.4 % SLOWER (teacher 5.351 / 5.356 ms with, 5.327 / 5.331 without; student
 // 7.639 vs 7.601).  Correct and tested (tests/test_gpu_vit_lnfold.py), not faster: off.
-#include <stdlib.h>
-
 #include "common.h"
 #include "gemm_variants.h"
 #include "medp_hip.h"
@@ -84,7 +82,7 @@ VitWs plan(const MedpVitWeights* w, int B, int H, int W) {
 
 int g_vit_lnfold = -1;          // medp_dbg_vit_lnfold (tests): 1 / 0 force the fold on / off, -1 the environment's choice
 bool fold_wanted(const MedpVitWeights* w, int M) {
-    static const int env_on = [] { const char* e = getenv("MEDP_VIT_LNFOLD"); return e ? atoi(e) : 0; }();
+    static const int env_on = medp_env_int("MEDP_VIT_LNFOLD", 0);
     const int on = g_vit_lnfold >= 0 ? g_vit_lnfold : env_on;
     const int D = w->hidden;
     if (!on || D % 256 != 0 || D / 256 > 4 || w->n_layers <= 0) return false;
@@ -94,6 +92,12 @@ bool fold_wanted(const MedpVitWeights* w, int M) {
     }
     return medp_gemm_fold_eligible(M, 3 * D, D) && medp_gemm_fold_eligible(M, w->mlp_hidden, D) && medp_gemm_fold_eligible(M, D, D) &&
            medp_gemm_fold_eligible(M, D, w->mlp_hidden);
+}
+
+// one block GEMM (tag 1: its own kernel symbols and the launch clock), dense operands: lda = ldw = K, ldc = ldr = N
+int block_gemm(const void* A, const void* W, void* C, int M, int N, int K, const float* bias, const float* scale, const float* residual,
+               int act, int out_bf16, const MedpGemmFold& fold, void* stream) {
+    return medp_gemm_run(MedpGemmArgs{A, W, C, M, N, K, K, K, N, bias, scale, residual, N, act, out_bf16, nullptr, 0, fold}, 1, nullptr, 0, stream);
 }
 }  // namespace
 
@@ -160,25 +164,26 @@ extern "C" int medp_vit_forward_part(const MedpVitWeights* w, const float* pixel
         for (int l = first_layer; l < last_layer; ++l) {
             const MedpVitLayer& L = w->layers[l];
             cons.colsum = L.qkv_cs;
-            MEDP_TRY(medp_gemm_bf16_nt_fold(xb, L.qkv_wg, qkv, M, 3 * D, D, D, D, 3 * D, L.qkv_b2, nullptr, nullptr, 0, 0, 1, cons, stream));
+            MEDP_TRY(block_gemm(xb, L.qkv_wg, qkv, M, 3 * D, D, L.qkv_b2, nullptr, nullptr, 0, 1, cons, stream));
             MEDP_TRY(medp_attn_fwd_dh64(qkv, (const bf16_t*)qkv + D, (const bf16_t*)qkv + 2 * D, att, B, S, w->n_heads, 3 * D, 3 * D,
                                         3 * D, D, scale, stream));
-            MEDP_TRY(medp_gemm_bf16_nt_fold(att, L.proj_w, x, M, D, D, D, D, D, L.proj_b, L.ls1, x, D, 0, 0, prod, stream));
+            MEDP_TRY(block_gemm(att, L.proj_w, x, M, D, D, L.proj_b, L.ls1, x, 0, 0, prod, stream));
             cons.colsum = L.fc1_cs;
-            MEDP_TRY(medp_gemm_bf16_nt_fold(xb, L.fc1_wg, f, M, w->mlp_hidden, D, D, D, w->mlp_hidden, L.fc1_b2, nullptr, nullptr, 0, 1, 1, cons, stream));
-            MEDP_TRY(medp_gemm_bf16_nt_fold(f, L.fc2_w, x, M, D, w->mlp_hidden, w->mlp_hidden, w->mlp_hidden, D, L.fc2_b, L.ls2, x, D, 0, 0, prod, stream));
+            MEDP_TRY(block_gemm(xb, L.fc1_wg, f, M, w->mlp_hidden, D, L.fc1_b2, nullptr, nullptr, 1, 1, cons, stream));
+            MEDP_TRY(block_gemm(f, L.fc2_w, x, M, D, w->mlp_hidden, L.fc2_b, L.ls2, x, 0, 0, prod, stream));
         }
     } else {
+        const MedpGemmFold plain{};
         for (int l = first_layer; l < last_layer; ++l) {
             const MedpVitLayer& L = w->layers[l];
             MEDP_TRY(medp_layernorm_fwd(x, D, L.ln1_w, L.ln1_b, h, D, 1, nullptr, nullptr, M, D, w->ln_eps, stream));
-            MEDP_TRY(medp_gemm_bf16_nt_tagged(1, h, L.qkv_w, qkv, M, 3 * D, D, D, D, 3 * D, L.qkv_b, nullptr, nullptr, 0, 0, 1, stream));
+            MEDP_TRY(block_gemm(h, L.qkv_w, qkv, M, 3 * D, D, L.qkv_b, nullptr, nullptr, 0, 1, plain, stream));
             MEDP_TRY(medp_attn_fwd_dh64(qkv, (const bf16_t*)qkv + D, (const bf16_t*)qkv + 2 * D, att, B, S, w->n_heads, 3 * D, 3 * D,
                                         3 * D, D, scale, stream));
-            MEDP_TRY(medp_gemm_bf16_nt_tagged(1, att, L.proj_w, x, M, D, D, D, D, D, L.proj_b, L.ls1, x, D, 0, 0, stream));
+            MEDP_TRY(block_gemm(att, L.proj_w, x, M, D, D, L.proj_b, L.ls1, x, 0, 0, plain, stream));
             MEDP_TRY(medp_layernorm_fwd(x, D, L.ln2_w, L.ln2_b, h, D, 1, nullptr, nullptr, M, D, w->ln_eps, stream));
-            MEDP_TRY(medp_gemm_bf16_nt_tagged(1, h, L.fc1_w, f, M, w->mlp_hidden, D, D, D, w->mlp_hidden, L.fc1_b, nullptr, nullptr, 0, 1, 1, stream));
-            MEDP_TRY(medp_gemm_bf16_nt_tagged(1, f, L.fc2_w, x, M, D, w->mlp_hidden, w->mlp_hidden, w->mlp_hidden, D, L.fc2_b, L.ls2, x, D, 0, 0, stream));
+            MEDP_TRY(block_gemm(h, L.fc1_w, f, M, w->mlp_hidden, D, L.fc1_b, nullptr, nullptr, 1, 1, plain, stream));
+            MEDP_TRY(block_gemm(f, L.fc2_w, x, M, D, w->mlp_hidden, L.fc2_b, L.ls2, x, 0, 0, plain, stream));
         }
     }
     if (!finish) return 0;                 // the fp32 token stream stays in the workspace for the call that continues
@@ -204,5 +209,6 @@ extern "C" int medp_dbg_gemm_fold(const void* A, const void* W, void* C, int M, 
     MedpGemmFold f{};
     f.c2 = c2; f.ldc2 = N; f.stats_out = stats_out;
     f.stats_in = stats_in; f.stats_tiles = stats_tiles; f.colsum = colsum; f.ln_eps = ln_eps; f.ln_dim = ln_dim;
-    return medp_gemm_bf16_nt_fold(A, W, C, M, N, K, K, K, N, bias, scale, residual, N, act, out_bf16, f, stream);
+    MEDP_CHECK_ARG(medp_gemm_fold_eligible(M, N, K), "gemm(fold): M=%d N=%d K=%d does not take the 256-tile kernels", M, N, K);
+    return block_gemm(A, W, C, M, N, K, bias, scale, residual, act, out_bf16, f, stream);
 }

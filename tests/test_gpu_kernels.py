@@ -96,6 +96,25 @@ def test_gemm_split_k_small_grids(M, N, K):
     assert_close(x, want + res.double(), 1e-4, 2e-4, "split-K in-place residual")
 
 
+@pytest.mark.parametrize("K", [72, 32])
+def test_gemm_v3_ragged_tiles(K):
+    """The 256 x 128-tile kernel (v3) under default dispatch (tests/test_gemm_plan_cpu.py pins that both shapes take it): 8130 rows end
+    inside the last row tile, 772 columns inside the last column tile, K = 72 inside a 32-deep K-tile; K = 32 is a single K-tile, both
+    prefetches zero-sourced.  fp64 product of the same bf16 operands; tolerances of test_gemm_plain / test_gemm_epilogue_and_strides."""
+    M, N = 8130, 772
+    a = bf_round(rnd(M, K, seed=21))
+    w = bf_round(rnd(N, K, seed=22) / math.sqrt(K))
+    bias, scale, res = rnd(N, seed=23), 1 + 0.1 * rnd(N, seed=24), rnd(M, N, seed=25)
+    ad, wd = a.to(DEV).bfloat16(), w.to(DEV).bfloat16()
+    want = a.double() @ w.double().T
+    assert_close(Fn.gemm(ad, wd), want, 1e-4, 2e-4, "v3 plain")
+    got16 = Fn.gemm(ad, wd, bias=bias.to(DEV), act=1, out_dtype=torch.bfloat16)
+    assert_close(got16, torch.nn.functional.gelu(want + bias.double()), 8e-3, 8e-3, "v3 bias+gelu -> bf16")
+    x = res.to(DEV).clone()
+    Fn.gemm(ad, wd, bias=bias.to(DEV), scale=scale.to(DEV), residual=x, out=x)
+    assert_close(x, (want + bias.double()) * scale.double() + res.double(), 2e-4, 3e-4, "v3 in-place residual")
+
+
 def test_gemm_rejects_bad_arguments():
     a = torch.zeros(8, 12, device=DEV, dtype=torch.bfloat16)
     w = torch.zeros(8, 12, device=DEV, dtype=torch.bfloat16)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Split-K sweep of DuETT's skinny GEMMs (forward shapes of both axes at cfg3, B 64): MEDP_GEMM_SPLITK is read once per process, so
 this script is run once per value:   for s in 0 1 2 3 4 6 8; do MEDP_GEMM_SPLITK=$s python tools/bench_gemm_splitk.py; done
-(0 = the heuristic of splitk_slices).  torch.matmul (hipBLASLt) beside each."""
+(0 = the heuristic of gemm_plan, csrc/gemm_bf16.hip).  torch.matmul (hipBLASLt) beside each."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -3,7 +3,7 @@
 ("the compiler emits the same instructions").  Needs hipcc, no GPU.
 
     python tools/diff_kernel_isa.py BASE [--work DIR] [--files a.hip ...] [--defines "" "MEDP_V7_PHASE_TRACE" ...] [--by-function]
-                                    [--merged NEW.hip=OLD1.hip,OLD2.hip ...]
+                                    [--merged NEW.hip=OLD1.hip,OLD2.hip ...] [--split OLD.hip=NEW1.hip,NEW2.hip ...]
 
 BASE is a git revision (its csrc/ and include/ are extracted to a temporary directory) or a directory holding a tree; the other side
 is the work tree (--work: another directory).  Every file is compiled for gfx950 at the flags of build.py with `-S --cuda-device-only`,
@@ -14,6 +14,7 @@ Prints IDENTICAL, REORDERED (every function and kernel descriptor identical and 
 change of the host code's template instantiation order does) or the first differing hunk per file and -D set; with --by-function a differing file is also listed function by
 function (for a change that deliberately removes or edits one kernel of a file).  --merged: NEW.hip of the work tree took over the
 kernels of several files of BASE; those are compiled one by one and NEW.hip is listed function by function against their union.
+--split: the reverse, OLD.hip of BASE was divided over several files of the work tree (OLD.hip itself may be one of them).
 Exit status 1 on any difference."""
 import argparse
 import concurrent.futures
@@ -102,6 +103,7 @@ def main() -> int:
     ap.add_argument("--defines", nargs="*", help='-D sets, comma-separated names, "" for none (default: "" and, for gemm_bf16_v7.hip, its switches)')
     ap.add_argument("--by-function", action="store_true", help="list the functions of a differing file one by one")
     ap.add_argument("--merged", nargs="*", default=[], metavar="NEW.hip=OLD1.hip,OLD2.hip", help="a work-tree file set against several files of the base")
+    ap.add_argument("--split", nargs="*", default=[], metavar="OLD.hip=NEW1.hip,NEW2.hip", help="a file of the base set against several work-tree files")
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 1))
     args = ap.parse_args()
 
@@ -109,6 +111,8 @@ def main() -> int:
         base = args.base if os.path.isdir(args.base) else extract(args.base, tmp)
         names = args.files or sorted(os.path.basename(f) for f in glob.glob(os.path.join(args.work, PKG, "csrc", "*.hip")))
         merged = {new: olds.split(",") for new, olds in (m.split("=") for m in args.merged)}
+        split = {old: news.split(",") for old, news in (m.split("=") for m in args.split)}
+        names = [n for n in names if n in split or not any(n in news for news in split.values())]
         jobs = []
         for n in names:
             for d in (args.defines if args.defines is not None else [""] + (V7_DEFINES if n == "gemm_bf16_v7.hip" else [])):
@@ -116,17 +120,23 @@ def main() -> int:
         with concurrent.futures.ThreadPoolExecutor(args.j) as pool:
             futs = {(t, n, d): pool.submit(assembly, t, n, d) for n, d in jobs for t in (base, args.work) if t == args.work or n not in merged}
             futs.update({(base, o, ""): pool.submit(assembly, base, o, "") for olds in merged.values() for o in olds})
+            futs.update({(args.work, x, ""): pool.submit(assembly, args.work, x, "") for news in split.values() for x in news})
             differ = 0
             for n, d in jobs:
                 label = n + (f" [-D{d}]" if d else "")
-                if n in merged:
-                    fa = {k: v for o in merged[n] for k, v in functions(normalise(futs[(base, o, "")].result())).items()}
-                    fb = functions(normalise(futs[(args.work, n, d)].result()))
+                if n in merged or n in split:
+                    if n in merged:
+                        fa = {k: v for o in merged[n] for k, v in functions(normalise(futs[(base, o, "")].result())).items()}
+                        fb = functions(normalise(futs[(args.work, n, d)].result()))
+                    else:
+                        fa = functions(normalise(futs[(base, n, d)].result()))
+                        fb = {k: v for x in split[n] for k, v in functions(normalise(futs[(args.work, x, "")].result())).items()}
                     states = {k: "only in base" if k not in fb else "only in work" if k not in fa else "identical" if fa[k] == fb[k] else "DIFFERENT"
                               for k in sorted(set(fa) | set(fb))}
                     same = sum(s == "identical" for s in states.values())
                     differ += same != len(states)
-                    print(f"MERGED     {label} <- {' + '.join(merged[n])}  ({same} of {len(states)} functions identical)")
+                    print(f"{'MERGED' if n in merged else 'SPLIT':10s} {label} {'<-' if n in merged else '->'} {' + '.join((merged if n in merged else split)[n])}"
+                          f"  ({same} of {len(states)} functions identical)")
                     for k, state in states.items():
                         print(f"    {state:13s} {k}")
                     continue
