@@ -267,11 +267,10 @@ typedef struct {
     int n_vars, n_static, d_embedding, n_heads, n_layers, d_ff, d_hidden_embed, d_hidden_tab, d_hidden_time, n_obs_rows,
         final_norm;
     float norm_eps;
-    /* per-variable embedding MLPs stacked over V: Linear(2,64) -> ReLU -> BN -> Linear(64,E)  (duett.py:84-86) */
-    const void *emb_w0, *emb_b0, *emb_bn_scale, *emb_bn_shift, *emb_w4, *emb_b4;   /* fp32 [V,64,2] [V,64] [V,64] [V,64] [V,E,64] [V,E] */
-    /* the same per-variable MLPs in the layout the fused embed kernel reads with SCALAR loads (weights are uniform over a
-     * workgroup): emb_l0 fp32 [V,64,8] = (w0[j][0], w0[j][1], b0[j], bn_scale[j], bn_shift[j], 0, 0, 0); emb_w4t fp32 [V,64,E] = w4 transposed */
-    const void *emb_l0, *emb_w4t;
+    /* per-variable embedding MLPs stacked over V: Linear(2,64) -> ReLU -> BN -> Linear(64,E)  (duett.py:84-86), in the layout the
+     * embed kernel stages in LDS: emb_b4 fp32 [V,E] = the second Linear's bias; emb_l0 fp32 [V,64,8] = (w0[j][0], w0[j][1], b0[j],
+     * bn_scale[j], bn_shift[j], 0, 0, 0); emb_w4t fp32 [V,64,E] = w4 transposed */
+    const void *emb_b4, *emb_l0, *emb_w4t;
     const void* n_obs_table;      /* fp32 [n_obs_rows] (n_obs_embedding.weight[:,0]) */
     const void *tab_w0, *tab_b0, *tab_bn_scale, *tab_bn_shift, *tab_w4, *tab_b4;   /* tab_encoder (duett.py:124-125) */
     const void* special;          /* fp32 [8, E] special_embeddings */

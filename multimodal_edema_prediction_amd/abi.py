@@ -40,7 +40,7 @@ class MedpDuettWeights(ctypes.Structure):
     _fields_ = ([(n, I) for n in ("n_vars", "n_static", "d_embedding", "n_heads", "n_layers", "d_ff", "d_hidden_embed",
                                   "d_hidden_tab", "d_hidden_time", "n_obs_rows", "final_norm")]
                 + [("norm_eps", F)]
-                + [(n, P) for n in ("emb_w0", "emb_b0", "emb_bn_scale", "emb_bn_shift", "emb_w4", "emb_b4", "emb_l0", "emb_w4t", "n_obs_table",
+                + [(n, P) for n in ("emb_b4", "emb_l0", "emb_w4t", "n_obs_table",
                                     "tab_w0", "tab_b0", "tab_bn_scale", "tab_bn_shift", "tab_w4", "tab_b4", "special",
                                     "time_w0", "time_b0", "time_bn_scale", "time_bn_shift", "time_w3t", "time_b3",
                                     "rep_embedding", "event_embedding")]

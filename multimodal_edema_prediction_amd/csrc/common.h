@@ -80,6 +80,9 @@ inline int medp_env_int(const char* name, int dflt) {
     return e ? atoi(e) : dflt;
 }
 
+// grid of a grid-stride kernel with 256-thread workgroups: one workgroup per 256 work items, at most `cap` of them
+inline int grid_for(size_t work_items, size_t cap = 4096) { return (int)min(cap, max((size_t)1, (work_items + 255) / 256)); }
+
 // device pointer (may be null) to a uint32 "RNG epoch" mixed into every dropout seed: lets a captured HIP graph draw a
 // fresh mask on every replay although the per-call seeds are baked into the graph (set by medp_rng_set_epoch_ptr)
 const uint32_t* medp_rng_epoch_ptr();

@@ -4,11 +4,10 @@
 // [G, R, C] so BatchNorm batch statistics and every weight gradient are plain column reductions — deterministic
 // two-stage sums, no float atomics.  All fp32; FLOPs are negligible, the cost is HBM traffic and launch count.
 #include "common.h"
+#include "duett_cells.h"
 #include "medp_hip.h"
 
 namespace {
-
-inline int grid_for(size_t work_items) { return (int)min((size_t)4096, max((size_t)1, (work_items + 255) / 256)); }
 
 // ---- grouped tiny linear: y[g][r][n] = b[g][n] + sum_k W[g][n][k] x[g][r][k]      (N*K <= 8192) ---------------------
 constexpr int GLINEAR_MAX_FLOATS = 36000;     // weights (+ bias) of one group held in LDS: 144 KB of the CU's 160 KB
@@ -267,17 +266,7 @@ __global__ __launch_bounds__(256) void embed_inputs_bwd_kernel(const float* __re
 }
 
 // ---- psi assembly (model :53-66) and its backward -------------------------------------------------------------------------
-// psi[b][t][v][:] = var_out[v][b*T+t][:] | tab_out[b][:] (v == V) | special[0] (masked timestep / masked event) | special[1] (t == T, event not masked at t = 0)
-__device__ __forceinline__ int psi_cell_kind(const float* __restrict__ xs, int b, int t, int v, int T, int V) {
-    // REP row; the reference extends the event mask to it with TIMESTEP 0's row (duett.py:250), so a variable whose event is masked
-    // there carries the MASKED embedding in the REP row too (every SSL batch: the masked event's count is -1 at all timesteps)
-    if (t == T) return (v < V && xs[(size_t)b * T * (2 * V + 1) + V + v] == -1.0f) ? 2 : 3;
-    const float* row = xs + ((size_t)b * T + t) * (2 * V + 1);
-    if (row[2 * V] == 1.0f) return 2;                       // masked timestep
-    if (v == V) return 1;                                   // static column
-    if (row[V + v] == -1.0f) return 2;                      // masked event
-    return 0;                                               // variable MLP output
-}
+// which source fills a cell: psi_cell_kind (duett_cells.h)
 __global__ __launch_bounds__(256) void psi_assemble_fwd_kernel(const float* __restrict__ xs, const float* __restrict__ var_out,
                                                                const float* __restrict__ tab_out, const float* __restrict__ special,
                                                                float* __restrict__ psi, int B, int T, int V, int E) {
@@ -290,8 +279,8 @@ __global__ __launch_bounds__(256) void psi_assemble_fwd_kernel(const float* __re
         c /= (V + 1);
         const int t = (int)(c % (T + 1)), b = (int)(c / (T + 1));
         const int kind = psi_cell_kind(xs, b, t, v, T, V);
-        const float* src = kind == 0 ? var_out + (((size_t)v * B + b) * T + t) * E : kind == 1 ? tab_out + (size_t)b * E
-                         : kind == 2 ? special : special + E;
+        const float* src = kind == PSI_VAR ? var_out + (((size_t)v * B + b) * T + t) * E : kind == PSI_STATIC ? tab_out + (size_t)b * E
+                         : kind == PSI_MASKED ? special : special + E;
         *(float4*)(psi + i * 4) = *(const float4*)(src + e4 * 4);
     }
 }
@@ -320,9 +309,9 @@ __global__ __launch_bounds__(256) void psi_assemble_bwd_kernel(const float* __re
             const int kind = psi_cell_kind(xs, b, t, v, T, V);
             const float4 g = *(const float4*)(dpsi + ((size_t)b * cells + cidx) * E + e4 * 4);
             if (v < V && t < T)
-                *(float4*)(d_var + (((size_t)v * B + b) * T + t) * E + e4 * 4) = kind == 0 ? g : make_float4(0.f, 0.f, 0.f, 0.f);
+                *(float4*)(d_var + (((size_t)v * B + b) * T + t) * E + e4 * 4) = kind == PSI_VAR ? g : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-            for (int k = 0; k < 3; ++k)
+            for (int k = 0; k < 3; ++k)          // PSI_STATIC, PSI_MASKED, PSI_REP
                 if (kind == k + 1) acc[k] = make_float4(acc[k].x + g.x, acc[k].y + g.y, acc[k].z + g.z, acc[k].w + g.w);
         }
 #pragma unroll

@@ -241,8 +241,6 @@ __global__ __launch_bounds__(256) void pos_bicubic_bwd_kernel(const float* __res
     }
 }
 
-inline int grid_for(size_t work_items) { return (int)min((size_t)4096, max((size_t)1, (work_items + 255) / 256)); }
-
 }  // namespace
 
 extern "C" int medp_cast_f32_bf16(const float* x, int ldx, void* y, int ldy, int rows, int cols, void* stream) {

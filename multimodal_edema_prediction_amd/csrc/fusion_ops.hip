@@ -6,7 +6,7 @@
 
 namespace {
 
-inline int grid_for(size_t work_items) { return (int)min((size_t)2048, max((size_t)1, (work_items + 255) / 256)); }
+constexpr size_t GRID_CAP = 2048;          // workgroups per launch here (grid_for, common.h)
 
 // y = dropout(gelu(x))                        (nn.GELU -> nn.Dropout, model :755, :573)
 template <bool Y16>
@@ -331,27 +331,27 @@ __global__ __launch_bounds__(256) void masked_bce_kernel(const float* __restrict
 
 extern "C" int medp_gelu_dropout_fwd(const float* x, float* y, long long n, float p, unsigned seed, unsigned stream_id, void* stream) {
     MEDP_CHECK_ARG(x && y && n > 0 && p >= 0.f && p < 1.f, "gelu_dropout_fwd: bad argument");
-    gelu_dropout_fwd_kernel<false><<<grid_for((size_t)n), 256, 0, (hipStream_t)stream>>>(x, y, (size_t)n, p, 1.f / (1.f - p), seed, stream_id, medp_rng_epoch_ptr());
+    gelu_dropout_fwd_kernel<false><<<grid_for((size_t)n, GRID_CAP), 256, 0, (hipStream_t)stream>>>(x, y, (size_t)n, p, 1.f / (1.f - p), seed, stream_id, medp_rng_epoch_ptr());
     MEDP_LAUNCH_CHECK("medp_gelu_dropout_fwd");
     return 0;
 }
 extern "C" int medp_gelu_dropout_fwd_bf16(const float* x, void* y_bf16, long long n, float p, unsigned seed, unsigned stream_id, void* stream) {
     MEDP_CHECK_ARG(x && y_bf16 && n > 0 && p >= 0.f && p < 1.f, "gelu_dropout_fwd_bf16: bad argument");
-    gelu_dropout_fwd_kernel<true><<<grid_for((size_t)n), 256, 0, (hipStream_t)stream>>>(x, y_bf16, (size_t)n, p, 1.f / (1.f - p), seed, stream_id, medp_rng_epoch_ptr());
+    gelu_dropout_fwd_kernel<true><<<grid_for((size_t)n, GRID_CAP), 256, 0, (hipStream_t)stream>>>(x, y_bf16, (size_t)n, p, 1.f / (1.f - p), seed, stream_id, medp_rng_epoch_ptr());
     MEDP_LAUNCH_CHECK("medp_gelu_dropout_fwd_bf16");
     return 0;
 }
 extern "C" int medp_gelu_dropout_bwd(const float* dy, const float* x, float* dx, long long n, float p, unsigned seed,
                                      unsigned stream_id, void* stream) {
     MEDP_CHECK_ARG(dy && x && dx && n > 0 && p >= 0.f && p < 1.f, "gelu_dropout_bwd: bad argument");
-    gelu_dropout_bwd_kernel<false><<<grid_for((size_t)n), 256, 0, (hipStream_t)stream>>>(dy, x, dx, nullptr, (size_t)n, p, 1.f / (1.f - p), seed, stream_id, medp_rng_epoch_ptr());
+    gelu_dropout_bwd_kernel<false><<<grid_for((size_t)n, GRID_CAP), 256, 0, (hipStream_t)stream>>>(dy, x, dx, nullptr, (size_t)n, p, 1.f / (1.f - p), seed, stream_id, medp_rng_epoch_ptr());
     MEDP_LAUNCH_CHECK("medp_gelu_dropout_bwd");
     return 0;
 }
 extern "C" int medp_gelu_dropout_bwd_bf16(const float* dy, const float* x, float* dx, void* dx_bf16, long long n, float p, unsigned seed,
                                           unsigned stream_id, void* stream) {
     MEDP_CHECK_ARG(dy && x && dx && dx_bf16 && n > 0 && p >= 0.f && p < 1.f, "gelu_dropout_bwd_bf16: bad argument");
-    gelu_dropout_bwd_kernel<true><<<grid_for((size_t)n), 256, 0, (hipStream_t)stream>>>(dy, x, dx, (bf16_t*)dx_bf16, (size_t)n, p, 1.f / (1.f - p), seed, stream_id,
+    gelu_dropout_bwd_kernel<true><<<grid_for((size_t)n, GRID_CAP), 256, 0, (hipStream_t)stream>>>(dy, x, dx, (bf16_t*)dx_bf16, (size_t)n, p, 1.f / (1.f - p), seed, stream_id,
                                                                                        medp_rng_epoch_ptr());
     MEDP_LAUNCH_CHECK("medp_gelu_dropout_bwd_bf16");
     return 0;
@@ -359,7 +359,7 @@ extern "C" int medp_gelu_dropout_bwd_bf16(const float* dy, const float* x, float
 extern "C" int medp_dropout_add(const float* y, const float* residual, float* out, long long n, float p, unsigned seed,
                                 unsigned stream_id, void* stream) {
     MEDP_CHECK_ARG(y && out && n > 0 && p >= 0.f && p < 1.f, "dropout_add: bad argument");
-    dropout_add_kernel<<<grid_for((size_t)n), 256, 0, (hipStream_t)stream>>>(y, residual, out, (size_t)n, p, 1.f / (1.f - p), seed, stream_id, medp_rng_epoch_ptr());
+    dropout_add_kernel<<<grid_for((size_t)n, GRID_CAP), 256, 0, (hipStream_t)stream>>>(y, residual, out, (size_t)n, p, 1.f / (1.f - p), seed, stream_id, medp_rng_epoch_ptr());
     MEDP_LAUNCH_CHECK("medp_dropout_add");
     return 0;
 }
@@ -379,7 +379,7 @@ extern "C" int medp_rowdot_bwd(const float* dy, const float* x, int ldx, const f
 extern "C" int medp_fusion_logits_fwd(const float* hi, const float* ht, const float* hc, const float* img_bias, const float* ts_bias,
                                       const float* beta, float* img, float* ts, float* scaled, float* fus, int B, int K, void* stream) {
     MEDP_CHECK_ARG(hi && ht && hc && img_bias && ts_bias && beta && img && ts && scaled && fus && B > 0 && K > 0, "fusion_logits_fwd: bad argument");
-    fusion_logits_fwd_kernel<<<grid_for((size_t)B * K), 256, 0, (hipStream_t)stream>>>(hi, ht, hc, img_bias, ts_bias, beta, img, ts, scaled, fus, B, K);
+    fusion_logits_fwd_kernel<<<grid_for((size_t)B * K, GRID_CAP), 256, 0, (hipStream_t)stream>>>(hi, ht, hc, img_bias, ts_bias, beta, img, ts, scaled, fus, B, K);
     MEDP_LAUNCH_CHECK("medp_fusion_logits_fwd");
     return 0;
 }
@@ -411,13 +411,13 @@ extern "C" int medp_student_kd_loss(const float* z_s, const float* z_t, const fl
 }
 extern "C" int medp_meanpool_fwd(const float* x, float* y, int B, int T, int T1, int D, void* stream) {
     MEDP_CHECK_ARG(x && y && B > 0 && T > 0 && T1 >= T && D > 0, "meanpool_fwd: bad argument");
-    meanpool_fwd_kernel<<<grid_for((size_t)B * D), 256, 0, (hipStream_t)stream>>>(x, y, B, T, T1, D);
+    meanpool_fwd_kernel<<<grid_for((size_t)B * D, GRID_CAP), 256, 0, (hipStream_t)stream>>>(x, y, B, T, T1, D);
     MEDP_LAUNCH_CHECK("medp_meanpool_fwd");
     return 0;
 }
 extern "C" int medp_meanpool_bwd(const float* dy, float* dx, int B, int T, int T1, int D, void* stream) {
     MEDP_CHECK_ARG(dy && dx && B > 0 && T > 0 && T1 >= T && D > 0, "meanpool_bwd: bad argument");
-    meanpool_bwd_kernel<<<grid_for((size_t)B * T1 * D), 256, 0, (hipStream_t)stream>>>(dy, dx, B, T, T1, D);
+    meanpool_bwd_kernel<<<grid_for((size_t)B * T1 * D, GRID_CAP), 256, 0, (hipStream_t)stream>>>(dy, dx, B, T, T1, D);
     MEDP_LAUNCH_CHECK("medp_meanpool_bwd");
     return 0;
 }

@@ -315,14 +315,9 @@ class Model(nn.Module):
         w.d_hidden_time = self.full_time_embedding[0].out_features
         w.n_obs_rows = self.n_obs_embedding.num_embeddings
         w.final_norm, w.norm_eps = int(FINAL_NORM), SCALENORM_EPS
-        w.emb_w0 = f32(torch.stack([m[0].weight for m in el]))
-        w.emb_b0 = f32(torch.stack([m[0].bias for m in el]))
         folded = [m[3].folded() for m in el]
-        w.emb_bn_scale = f32(torch.stack([s for s, _ in folded]))
-        w.emb_bn_shift = f32(torch.stack([b for _, b in folded]))
-        w.emb_w4 = f32(torch.stack([m[4].weight for m in el]))
         w.emb_b4 = f32(torch.stack([m[4].bias for m in el]))
-        # scalar-load layout of the same MLPs for the fused embed kernel (include/medp_hip.h)
+        # the first Linear and the folded BatchNorm in the embed kernel's LDS layout (include/medp_hip.h)
         w0s, b0s = torch.stack([m[0].weight for m in el]).detach(), torch.stack([m[0].bias for m in el]).detach()
         l0 = torch.zeros((V, w0s.shape[1], 8), dtype=torch.float32, device=w0s.device)
         l0[..., 0:2], l0[..., 2] = w0s, b0s

@@ -1,4 +1,4 @@
-"""The fused DuETT front end (csrc/duett.hip): `medp_duett_embed_fwd` — psi built directly in the event view with the event
+"""The fused DuETT front end (csrc/duett_embed.hip, csrc/duett.hip): `medp_duett_embed_fwd` — psi built directly in the event view with the event
 embedding added and the first ScaleNorm applied, and the time embedding — and `medp_duett_swap_add_norm` (axis swap + positional
 add + the next encoder's ScaleNorm in one pass), against the CPU oracle (oracle/duett_ref.py, pinned by the reference's fixtures)
 and against the separate launches they replace (bit-identical ScaleNorm)."""
@@ -61,6 +61,106 @@ def test_embed_stage_against_oracle(B, T, V):
     assert torch.equal(h, Fn.scalenorm(xe, m.event_transformers[0].layers[0][0][0].g))               # == the separate launch, bit for bit
 
 
+def _eval_backbone(T, V, DS=8):
+    """The synthetic frozen backbone in eval() with non-trivial BatchNorm running statistics: (module on the GPU, CPU state dict)."""
+    from multimodal_edema_prediction_amd.main_architecture_duett import load_duett_backbone
+    m = load_duett_backbone("synthetic", d_static_num=DS, d_time_series_num=V, n_timesteps=T, freeze=True)
+    with torch.no_grad():
+        for n, b in m.named_buffers():
+            if n.endswith("running_mean"):
+                b.copy_(0.1 * torch.randn_like(b))
+            elif n.endswith("running_var"):
+                b.copy_(0.5 + torch.rand_like(b))
+        m.event_transformers[0].layers[0][0][0].g.fill_(1.3)
+    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    return m.to(DEV).eval(), sd
+
+
+def _ssl_like_batch(B, T, V, DS=8):
+    """kernel_refs.ssl_like_inputs with a static vector and bin times; asserts that the batch holds what the REP-row rule is about:
+    a (b, v) whose count is -1 at t = 0 while timestep 0 itself is not masked.  Returns (xs_static, xs_ts, xs_times, such (b, v))."""
+    import kernel_refs as KR
+    g = torch.Generator().manual_seed(100 * T + V)
+    xs_ts = KR.ssl_like_inputs(B, T, V, g)
+    hit = ((xs_ts[:, 0, V:2 * V] == -1) & (xs_ts[:, 0, 2 * V] != 1).unsqueeze(1)).nonzero()
+    assert len(hit) > 0, "no event masked at t = 0 under an unmasked timestep 0: the REP-row rule would go untested"
+    return torch.randn(B, DS, generator=g), xs_ts, torch.rand(B, T, generator=g) * 4, hit
+
+
+@pytest.mark.parametrize("B,T,V", [(3, 5, 4), (2, 70, 3), (2, 140, 3)])          # one, two and three passes of the 64-lane cell loop
+def test_embed_stage_against_oracle_with_masked_events(B, T, V, request):
+    """The embed kernel on an SSL-like batch (masked events, one of them at every step; masked timesteps, step 0 among them; a
+    variable masked at step 0 only) against oracle/duett_ref.build_psi with predict_events.  The reference extends the event mask to
+    the REP row with timestep 0's mask, so a variable whose count is -1 at t = 0 carries special[0] in the REP row, not special[1]:
+    every overridden cell must be bit-equal to its special row, in the matrix-core and in the VALU form.  (The embed kernel's own copy
+    of the rule wrote special[1] into every REP cell: 2 or 3 cells off per shape, |psi0 - oracle| up to 3.2.)"""
+    from oracle import duett_ref
+    E = 24
+    torch.manual_seed(T)
+    m, sd = _eval_backbone(T, V)
+    xs_static, xs_ts, xs_times, hit = _ssl_like_batch(B, T, V)
+    cfg = duett_ref.DuettCfg(d_static_num=xs_static.shape[1], d_time_series_num=V, n_timesteps=T)
+    psi0, temb_ref = duett_ref.build_psi(sd, cfg, xs_static, xs_ts, xs_times, training=False, predict_events=True)
+    special = sd["special_embeddings.weight"]
+    assert not torch.equal(special[0], special[1])
+    for b, v in hit.tolist():                                  # not vacuous: the oracle's REP cell there is the MASKED embedding
+        assert torch.equal(psi0[b, T, v], special[0]) and not torch.equal(psi0[b, T, v], special[1])
+    # the override masks, as build_psi forms them
+    ev = torch.cat((xs_ts[:, :, V:2 * V] == -1, torch.zeros((B, T, 1), dtype=torch.bool)), dim=2)
+    masked = torch.cat((ev, ev[:, :1, :]), dim=1) | torch.cat((xs_ts[:, :, -1] == 1, torch.zeros((B, 1), dtype=torch.bool)), dim=1).unsqueeze(2)
+    rep = ~masked
+    rep[:, :T] = False
+    xe_ref = psi0.transpose(1, 2).flatten(2) + sd["full_event_embedding.weight"]          # model :80
+    h_ref = torch.nn.functional.normalize(xe_ref, dim=-1) * xe_ref.shape[-1] ** 0.5 * sd["event_transformers.0.layers.0.0.0.g"]
+
+    w = m._prepare()[0]
+    T1, V1 = T + 1, V + 1
+    dev = [t.to(DEV) for t in (xs_static, xs_ts, xs_times)]
+    L = lib()
+    prev = L.medp_dbg_embed_mfma(1)
+    request.addfinalizer(lambda: L.medp_dbg_embed_mfma(prev))
+    for form in (1, 0):
+        L.medp_dbg_embed_mfma(form)
+        xe = torch.full((B, V1, T1 * E), float("nan"), device=DEV)
+        h = torch.zeros((B, V1, T1 * E), device=DEV, dtype=torch.bfloat16)
+        temb = torch.full((B, T1, V1 * E), float("nan"), device=DEV)
+        p0 = torch.full((B, T1, V1, E), float("nan"), device=DEV)
+        tab = torch.empty((B, E), device=DEV)
+        check(L.medp_duett_embed_fwd(ctypes.byref(w), ptr(dev[0]), ptr(dev[1]), ptr(dev[2]), B, T, ptr(xe), ptr(h), ptr(temb), ptr(p0), ptr(tab),
+                                     3, stream()), "duett_embed_fwd")
+        p0c = p0.cpu()
+        print(f"form {form}: psi0 {float((p0c - psi0).abs().max()):.3e}  xe {float((xe.cpu() - xe_ref).abs().max()):.3e}  "
+              f"masked cells off {int((p0c[masked] != special[0]).any(-1).sum())} of {int(masked.sum())}  "
+              f"REP cells off {int((p0c[rep] != special[1]).any(-1).sum())} of {int(rep.sum())}")
+        assert float((p0c - psi0).abs().max()) < 2e-5, form
+        assert torch.equal(p0c[masked], special[0].expand(int(masked.sum()), E)), form
+        assert torch.equal(p0c[rep], special[1].expand(int(rep.sum()), E)), form
+        assert float((xe.cpu() - xe_ref).abs().max()) < 2e-5, form
+        assert float((temb.cpu() - temb_ref).abs().max()) < 2e-5, form
+        assert float((h.float().cpu() - h_ref).abs().max()) < 8e-3 * float(h_ref.abs().max()), form      # bf16 output
+        assert torch.equal(h, Fn.scalenorm(xe, m.event_transformers[0].layers[0][0][0].g)), form         # == the separate launch, bit for bit
+
+
+def test_inference_and_training_forms_agree_on_masked_events():
+    """`_encode_inference` (one C call, the embed kernel) and `encode_training` (op-level form, psi_assemble) on one frozen eval()
+    backbone and one SSL-like batch: the same tokens, within the bound the suite puts on either form against the reference's eval-mode
+    encode (test_gpu_model.py, test_gpu_student.py: 3e-2).  Before the embed kernel took the shared cell rule this failed at the REP
+    row: a variable whose count is -1 at t = 0 got special[1] there from the inference form and special[0] from the training form
+    (measured on that commit: max 4.9e-1, all of it in the REP row; 5.8e-3 with the shared rule)."""
+    from multimodal_edema_prediction_amd.duett_train import encode_training
+    B, T, V = 3, 5, 4
+    torch.manual_seed(5)
+    m, _ = _eval_backbone(T, V)
+    xs_static, xs_ts, xs_times, _ = _ssl_like_batch(B, T, V)
+    xin = (xs_static.to(DEV), xs_ts.to(DEV), xs_times.to(DEV), [T] * B)
+    with torch.no_grad():
+        inf = m._encode_inference(xin)[0]
+        trn = encode_training(m, xin)
+    err = (inf - trn).abs()
+    print(f"inference vs training form: max {float(err.max()):.3e} (REP row {float(err[:, T].max()):.3e}), mean {float(err.mean()):.3e}")
+    assert float(err.max()) < 3e-2
+
+
 @pytest.mark.parametrize("B,T,V", [(8, 32, 16), (6, 96, 48), (2, 140, 20)])
 def test_embed_stage_mfma_form_is_bit_identical_to_the_valu_form(B, T, V, request):
     """The psi / time embeddings on the matrix cores in exact fp32 (`v_mfma_f32_16x16x4_f32`: a k-ordered fmaf chain) against the
@@ -86,6 +186,7 @@ def test_embed_stage_mfma_form_is_bit_identical_to_the_valu_form(B, T, V, reques
     xs_ts[:, :, V:2 * V][torch.rand(B, T, V, generator=g) < 0.05] = -1.0                            # masked events (SSL)
     xs_ts[:, :, 2 * V] = (torch.rand(B, T, generator=g) < 0.15).float()                            # masked time steps
     xs_ts[0, :, 2 * V] = 1.0                                                                         # a sample with every step masked
+    xs_ts[1, 0, V], xs_ts[1, 0, 2 * V] = -1.0, 0.0                                                   # an event masked at t = 0: its REP cell is special[0]
     xs_static, xs_times = torch.randn(B, DS, generator=g), torch.rand(B, T, generator=g) * 4
     xs_ts, xs_static, xs_times = xs_ts.to(DEV), xs_static.to(DEV), xs_times.to(DEV)
     w = m._prepare()[0]
