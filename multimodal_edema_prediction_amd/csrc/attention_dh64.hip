@@ -4,8 +4,8 @@
 // One 256-thread workgroup = 4 waves of one (batch, head).  The ceil(S/16) 16-query subtiles are dealt evenly over the
 // 4*gridDim.x waves (1..3 subtiles per wave, one pass each): for S = 257 that is two workgroups per (b, h) with one wave
 // carrying the odd CLS subtile, instead of a third workgroup that stages all of K/V for a single query.
-// K and V for a chunk of up to 320 keys sit in LDS (row-major [key][64], 128-B rows, XOR-swizzled 16-B
-// chunks, filled by LDS-DMA) and are shared by the 4 waves.  Per 64-key block a wave computes
+// K and V for a chunk of up to 320 keys sit in LDS (the swizzled row-major image of attention_dh64_tile.h, filled by LDS-DMA)
+// and are shared by the 4 waves.  Per 64-key block a wave computes
 //   S^T = K Q^T   (MFMA 16x16x32, A := K rows, B := Q rows -> key on the accumulator rows, query on the lane)
 // so a query's scores live on ONE lane column: the online-softmax statistics are per lane, the running
 // rescale multiplies whole registers, and the exponentiated tile is ALREADY the B operand of
@@ -15,15 +15,10 @@
 // "full block" vs "ragged tail"; the softmax is max / fma / v_exp_f32 / add per score (scale folded into the fma, bare
 // hardware exp2, scalar f32 ops — see key_block), and the 4-lane max butterfly uses v_permlane16/32_swap (VALU) instead
 // of ds_bpermute round trips.
-#include "common.h"
+#include "attention_dh64_tile.h"
 #include "medp_hip.h"
 
 namespace {
-
-__device__ __attribute__((aligned(16))) uint32_t g_zero16_attn[4] = {0, 0, 0, 0};
-
-constexpr int KC = 320;   // most keys per LDS chunk (5 blocks of 64)
-constexpr int NQ = 3;     // most 16-query subtiles one wave carries
 
 struct AttnParams {
     const bf16_t *q, *k, *v;
@@ -68,10 +63,8 @@ __device__ __forceinline__ void key_block(WaveState<NQW>& w, const char* sK, con
             for (int qs = 0; qs < NQW; ++qs) st[qs][kt] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
             continue;
         }
-        const int krow = kb * 64 + kt * 16 + fr;
-        const char* base = sK + krow * 128;
-        const bf16x8 k0 = *(const bf16x8*)(base + (((0 + kq) ^ (krow & 7)) << 4));
-        const bf16x8 k1 = *(const bf16x8*)(base + (((4 + kq) ^ (krow & 7)) << 4));
+        bf16x8 k0, k1;
+        img_frag(sK, kb * 64 + kt * 16 + fr, kq, k0, k1);
 #pragma unroll
         for (int qs = 0; qs < NQW; ++qs) {
             f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -140,30 +133,19 @@ __device__ __forceinline__ void key_block(WaveState<NQW>& w, const char* sK, con
         }
     }
     // ---- O^T += V^T P^T ----------------------------------------------------------------------------------------------
-    const int tr_q = fr >> 2, tr_p = fr & 3;   // tr-read lane geometry: lane 4*qq+pp of a 16-lane group -> row qq, columns 4pp..4pp+3
+    const int tr_q = fr >> 2, tr_p = fr & 3;   // tr-read lane geometry (img_tr_off)
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
         if (MASKED && 2 * ks >= ktv) continue;
         bf16x8 pf[NQW];
 #pragma unroll
-        for (int qs = 0; qs < NQW; ++qs) {
-            const f32x4 a = st[qs][2 * ks], b = st[qs][2 * ks + 1];
-            union { bf16x8 v; uint32_t u[4]; } pk;
-            pk.u[0] = pack_bf2(a[0], a[1]);
-            pk.u[1] = pack_bf2(a[2], a[3]);
-            pk.u[2] = pack_bf2(b[0], b[1]);
-            pk.u[3] = pack_bf2(b[2], b[3]);
-            pf[qs] = pk.v;
-        }
+        for (int qs = 0; qs < NQW; ++qs) pf[qs] = pack8(st[qs][2 * ks], st[qs][2 * ks + 1]);
         // k slot j of lane group kq: j<4 -> key base0 + 4kq + j ; j>=4 -> key base1 + 4kq + (j-4)
         const int key0 = kb * 64 + (2 * ks) * 16 + kq * 4 + tr_q;
         const int key1 = key0 + 16;
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-            const int chunk = dt * 2 + (tr_p >> 1), off = (tr_p & 1) * 8;
-            const bf16x4 v0 = lds_tr16(sV + key0 * 128 + ((chunk ^ (key0 & 7)) << 4) + off);
-            const bf16x4 v1 = lds_tr16(sV + key1 * 128 + ((chunk ^ (key1 & 7)) << 4) + off);
-            const bf16x8 vf = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+            const bf16x8 vf = img_tr_rows(sV, key0, key1, dt, tr_p);
 #pragma unroll
             for (int qs = 0; qs < NQW; ++qs) w.o[qs][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qs], w.o[qs][dt], 0, 0, 0);
         }
@@ -202,13 +184,8 @@ __device__ __forceinline__ void wave_body(const AttnParams& p, char* sK, char* s
         if (c0 > 0) __syncthreads();   // previous chunk fully consumed
         // ---- stage K, V chunk (LDS-DMA, swizzle on the source chunk index) -----------------
         for (int i = 0; i < niter; ++i) {
-            const int qd = i * NT + tid;
-            const int row = qd >> 3, c = (qd & 7) ^ (row & 7);
-            if (NT > 256 && row >= p.crows) break;                // (wave-uniform: a wave's 64 pieces are 8 whole rows, crows % 32 == 0)
-            const bool ok = row < nkeys;
-            const size_t grow = row0 + c0 + row;
-            glds16(ok ? p.k + grow * p.ldk + h * 64 + c * 8 : zero, sK + (i * NT + wave * 64) * 16);
-            glds16(ok ? p.v + grow * p.ldv + h * 64 + c * 8 : zero, sV + (i * NT + wave * 64) * 16);
+            if (NT > 256 && img_piece_row<NT>(i, tid) >= p.crows) break;      // (wave-uniform: a wave's 64 pieces are 8 whole rows, crows % 32 == 0)
+            img_stage_piece<NT>(p.k, p.ldk, p.v, p.ldv, zero, sK, sV, row0 + c0, nkeys, h, i, tid, wave);
         }
         MEDP_WAIT_LDS_DMA();           // the chunk's LDS-DMA has landed ...
         __syncthreads();               // ... before any wave reads it
@@ -245,13 +222,13 @@ __device__ __forceinline__ void wave_body(const AttnParams& p, char* sK, char* s
 __global__ __launch_bounds__(256, 2) void attn_fwd_dh64_kernel(const AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sK = smem;
-    char* sV = smem + p.crows * 128;   // crows = min(KC, S rounded up to 32): 288 rows at S = 257, so TWO workgroups fit a CU
+    char* sV = smem + p.crows * IMG_ROW;
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.z, h = blockIdx.y;
     const int ntile = (p.S + 15) >> 4, nwave = gridDim.x * 4, gw = blockIdx.x * 4 + wave;
     const int tbase = ntile / nwave, trem = ntile % nwave;
-    const int nq = tbase + (gw < trem ? 1 : 0);                 // subtiles of this wave (wave-uniform, <= NQ)
+    const int nq = tbase + (gw < trem ? 1 : 0);                 // subtiles of this wave (wave-uniform, <= 3)
     const int q0 = (gw * tbase + min(gw, trem)) * 16;
     if (nq == 3) wave_body<3>(p, sK, sV, q0, b, h, tid, wave);
     else if (nq == 2) wave_body<2>(p, sK, sV, q0, b, h, tid, wave);
@@ -264,12 +241,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_dh64_kernel(const AttnParams 
 // CU 8 waves to hide the softmax chains behind; here 6 workgroups of 8 waves stage it for 14.3 subtiles each and a CU holds 16 waves
 // (capped at 128 VGPRs: 10 spilled registers cost less than the second workgroup per CU gains — 268.8 us against 325.1 uncapped at
 // B 32, S 1370, H 12; the 4-wave kernel: 292.5; S 1025: 174.5 / 208.7; S 577: 75.9 / 82.4).
-__device__ __forceinline__ void w8_body(const AttnParams& p);
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_fwd_dh64_w8_kernel(const AttnParams p) { w8_body(p); }
 __device__ __forceinline__ void w8_body(const AttnParams& p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sK = smem;
-    char* sV = smem + p.crows * 128;
+    char* sV = smem + p.crows * IMG_ROW;
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.z, h = blockIdx.y;
@@ -281,6 +256,7 @@ __device__ __forceinline__ void w8_body(const AttnParams& p) {
     else if (nq == 1) wave_body<1, 512, true>(p, sK, sV, q0, b, h, tid, wave);
     else wave_body<0, 512, true>(p, sK, sV, q0, b, h, tid, wave);
 }
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_fwd_dh64_w8_kernel(const AttnParams p) { w8_body(p); }
 
 // ---- S = 257 (ViT-B/14 at 224 x 224: the class token + 256 patches): one 512-thread workgroup per (batch, head) ----------------------
 // The general kernel above cuts a (b, h) into two workgroups that EACH stage all of K / V, deals 17 query subtiles over 8 waves
@@ -291,13 +267,14 @@ __device__ __forceinline__ void w8_body(const AttnParams& p) {
 // split over the 8 waves (32 keys each, wave 0 also key 256), partial (m, l, O) combined through 2 KB of LDS by wave 7.
 constexpr int S257 = 257, CR257 = 288;
 constexpr int SCR_LD = 68;                                   // floats per wave in the class-query scratch: 64 O + m + l (+ pad)
-constexpr int LDS_257 = 2 * CR257 * 128 + 8 * SCR_LD * 4;
+constexpr int LDS_257 = 2 * CR257 * IMG_ROW + 8 * SCR_LD * 4;
 
-// One work unit of the S = 257 kernel: the patch-query subtiles t0 .. t0 + NQW - 1 of (b, h) for this wave (NQW = 2: a whole (b, h) per
-// workgroup, wave w takes subtiles 2w, 2w+1; NQW = 1: HALF a (b, h), wave w takes subtile 8 half + w) and, when `do_cls`, the class query.
-template <int NQW>
-__device__ __forceinline__ void s257_unit(const AttnParams& p, char* sK, char* sV, float* scr, int b, int h, int t0, bool do_cls, int tid,
-                                          int wave) {
+// One (b, h) of the S = 257 kernel, for one wave: its two patch-query subtiles t0 = 2 wave, t0 + 1 and its share of the class query.
+// Held to the instructions it had before attention_dh64_tile.h existed, register for register (the counted waits below), so the shared
+// helpers come in the forms that keep them: img_frag through a lambda, the class query's transposed read as IMG_TR_ROWS, and stage_pass
+// with its own block-ordered addressing (img_stage_piece<512> at tid = 64 wsrc + lane is the same piece but another prologue).
+__device__ __forceinline__ void s257_unit(const AttnParams& p, char* sK, char* sV, float* scr, int b, int h, int t0, int tid, int wave) {
+    constexpr int NQW = 2;
     const int lane = tid & 63, fr = lane & 15, kq = lane >> 4;
     const bf16_t* zero = (const bf16_t*)g_zero16_attn;
     const size_t row0 = (size_t)b * S257;
@@ -306,13 +283,13 @@ __device__ __forceinline__ void s257_unit(const AttnParams& p, char* sK, char* s
     // ---- loads, in the order they are needed, every wave the SAME number of vector-memory operations (vmcnt retires in order):
     //   2 LDS-DMA pieces: K / V rows 256..287 (key 256 initialises the online softmax; waves 4-7 rewrite the pieces of waves 0-3 with the
     //                     same bytes, so that the counts below hold for every wave)
-    //   2 NQW + 2 register loads: the Q fragments (inline asm: beside LDS-DMA hipcc would retire the WHOLE queue at the first use of an
+    //   6 register loads: the Q fragments (inline asm: beside LDS-DMA hipcc would retire the WHOLE queue at the first use of an
     //                     ordinary load's result — cdna guide §5 trap (b) — and the key blocks below could not start before the last row landed)
     //   8 LDS-DMA pieces: K / V rows 64 i .. 64 i + 63 = key block i, i = 0..3
     // Key block i waits for "all but the 2 (3 - i) youngest" and a raw barrier (every wave has then passed ITS wait): the first block runs
     // while three quarters of K / V are still in flight — the launch reads 76 MB and writes 25 MB, HBM time is what bounds it.
     auto stage_pass = [&](int i, int wsrc) {
-        const int row = i * 64 + (wsrc * 8 + (lane >> 3)), ch = (lane & 7) ^ (row & 7);
+        const int row = i * 64 + (wsrc * 8 + (lane >> 3)), ch = IMG_CHUNK(lane & 7, row);
         const bool ok = row < S257;
         const size_t grow = row0 + row;
         glds16(ok ? p.k + grow * p.ldk + h * 64 + ch * 8 : zero, sK + (i * 512 + wsrc * 64) * 16);
@@ -326,24 +303,17 @@ __device__ __forceinline__ void s257_unit(const AttnParams& p, char* sK, char* s
     for (int s2 = 0; s2 < 2; ++s2) {
 #pragma unroll
         for (int qs = 0; qs < NQW; ++qs) ld16(w.qf[qs][s2], p.q + (row0 + 1 + (t0 + qs) * 16 + fr) * p.ldq + h * 64 + s2 * 32 + kq * 8);
-        ld16(qc[s2], (do_cls && fr == 0) ? p.q + row0 * p.ldq + h * 64 + s2 * 32 + kq * 8 : zero);
+        ld16(qc[s2], fr == 0 ? p.q + row0 * p.ldq + h * 64 + s2 * 32 + kq * 8 : zero);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) stage_pass(i, wave);
     // rows 256..287 and the Q fragments have landed (8 pieces may still fly); the asm names the fragments so that no use moves above it
-    if constexpr (NQW == 2)
-        asm volatile("s_waitcnt vmcnt(8)" : "+v"(w.qf[0][0]), "+v"(w.qf[0][1]), "+v"(w.qf[1][0]), "+v"(w.qf[1][1]), "+v"(qc[0]), "+v"(qc[1])::"memory");
-    else
-        asm volatile("s_waitcnt vmcnt(8)" : "+v"(w.qf[0][0]), "+v"(w.qf[0][1]), "+v"(qc[0]), "+v"(qc[1])::"memory");
+    asm volatile("s_waitcnt vmcnt(8)" : "+v"(w.qf[0][0]), "+v"(w.qf[0][1]), "+v"(w.qf[1][0]), "+v"(w.qf[1][1]), "+v"(qc[0]), "+v"(qc[1])::"memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 
     const int tr_q = fr >> 2, tr_p = fr & 3;
-    auto k_frag = [&](int krow, bf16x8& k0, bf16x8& k1) {
-        const char* base = sK + krow * 128;
-        k0 = *(const bf16x8*)(base + (((0 + kq) ^ (krow & 7)) << 4));
-        k1 = *(const bf16x8*)(base + (((4 + kq) ^ (krow & 7)) << 4));
-    };
+    auto k_frag = [&](int krow, bf16x8& k0, bf16x8& k1) { img_frag(sK, krow, kq, k0, k1); };
     // ---- patch queries: the online softmax starts from key 256 (tile 16, row 0 of it) ------------------------------------------------
     {
         bf16x8 k0, k1;
@@ -360,7 +330,7 @@ __device__ __forceinline__ void s257_unit(const AttnParams& p, char* sK, char* s
             for (int dt = 0; dt < 4; ++dt) {
                 // (read as a bf16 vector like every other read of the staged images: a `uint2`-typed read made hipcc put s_waitcnt vmcnt(0)
                 //  in front of it — it may alias the LDS-DMA in flight — and the key blocks waited for the whole of K / V again)
-                const bf16x4 vq = *(const bf16x4*)(sV + 256 * 128 + dt * 32 + d0 * 2);       // row 256: 256 & 7 == 0, no swizzle
+                const bf16x4 vq = *(const bf16x4*)(sV + 256 * IMG_ROW + dt * 32 + d0 * 2);       // row 256: 256 & 7 == 0, no swizzle
                 const uint2 vv = __builtin_bit_cast(uint2, vq);
                 w.o[qs][dt] = (f32x4){__uint_as_float(vv.x << 16), __uint_as_float(vv.x & 0xffff0000u),
                                       __uint_as_float(vv.y << 16), __uint_as_float(vv.y & 0xffff0000u)};
@@ -396,7 +366,7 @@ __device__ __forceinline__ void s257_unit(const AttnParams& p, char* sK, char* s
         }
     }
     // ---- class query (all of K / V has landed by now): this wave's keys 32 wave .. 32 wave + 31 (key tiles 2 wave, 2 wave + 1); wave 0 also key 256 (tile 16) -------
-    if (do_cls) {                                             // (workgroup-uniform)
+    {
         f32x4 st[3];
         bf16x8 k0, k1;
 #pragma unroll
@@ -433,19 +403,12 @@ __device__ __forceinline__ void s257_unit(const AttnParams& p, char* sK, char* s
         for (int ks = 0; ks < 2; ++ks) {
             if (ks == 1 && wave != 0) break;
             const f32x4 a = st[2 * ks], b2 = ks == 0 ? st[1] : (f32x4){0.f, 0.f, 0.f, 0.f};
-            union { bf16x8 v; uint32_t u[4]; } pk;
-            pk.u[0] = pack_bf2(a[0], a[1]);
-            pk.u[1] = pack_bf2(a[2], a[3]);
-            pk.u[2] = pack_bf2(b2[0], b2[1]);
-            pk.u[3] = pack_bf2(b2[2], b2[3]);
+            const bf16x8 pk = pack8(a, b2);
             const int key0 = (ks == 0 ? 2 * wave : 16) * 16 + kq * 4 + tr_q, key1 = key0 + 16;      // (tile 17 = rows 272..287: zeros)
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
-                const int chunk = dt * 2 + (tr_p >> 1), off = (tr_p & 1) * 8;
-                const bf16x4 v0 = lds_tr16(sV + key0 * 128 + ((chunk ^ (key0 & 7)) << 4) + off);
-                const bf16x4 v1 = lds_tr16(sV + key1 * 128 + ((chunk ^ (key1 & 7)) << 4) + off);
-                const bf16x8 vf = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-                oc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pk.v, oc[dt], 0, 0, 0);
+                const bf16x8 vf = IMG_TR_ROWS(sV, key0, key1, dt, tr_p);
+                oc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pk, oc[dt], 0, 0, 0);
             }
         }
         if (fr == 0) {                                        // column 0 = the class query: O[d = 16 dt + 4 kq + r]
@@ -471,25 +434,22 @@ __device__ __forceinline__ void s257_unit(const AttnParams& p, char* sK, char* s
             if (p.lse && lane == 0) p.lse[((size_t)b * p.H + h) * S257] = M * c + __log2f(L);
         }
     }
-
 }
 
-// NQW = 2: workgroup i does the whole (b, h) = item0 + i (two subtiles per wave).  NQW = 1: workgroup i does HALF of (b, h) = item0 + i / 2
-// (8 query subtiles, one per wave; the even half also the class query), staging K / V for it.  The launcher runs the (b, h) that fill
-// whole rounds of the 2-per-CU resident slots as <2> and a remainder of at most half a round as <1> halves: B H = 768 on 512 slots is one
-// round of whole units + one round of half units (1.55 unit-times) instead of a second round that leaves every second slot idle (2).
-template <int NQW>
+// Workgroup i does the whole (b, h) = i.  Measured and removed: the (b, h) past whole rounds of the 2-per-CU resident slots as two HALF
+// units each (8 subtiles, one per wave) — B 64, H 12 (768 (b, h) on 512 slots): 37.8 us against 32.2 us for whole units only.  A (b, h)'s
+// cost is its 99 KB of loads, not its 16 subtiles of arithmetic, and a half unit stages all of K / V for half the queries.
+// `item0` (always 0) is what is left of it: without it the kernel-argument load moves and is waited for inside the staging sequence.
 __global__ __launch_bounds__(512, 2) void attn_fwd_dh64_s257_kernel(const AttnParams p, const int item0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sK = smem;
-    char* sV = smem + CR257 * 128;
-    float* scr = (float*)(smem + 2 * CR257 * 128);
+    char* sV = smem + CR257 * IMG_ROW;
+    float* scr = (float*)(smem + 2 * CR257 * IMG_ROW);
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int item = item0 + (NQW == 2 ? (int)blockIdx.x : (int)(blockIdx.x >> 1));
-    const int half = NQW == 2 ? 0 : (int)(blockIdx.x & 1);
+    const int item = item0 + (int)blockIdx.x;
     const int b = item / p.H, h = item - b * p.H;
-    s257_unit<NQW>(p, sK, sV, scr, b, h, NQW == 2 ? 2 * wave : 8 * half + wave, half == 0, tid, wave);
+    s257_unit(p, sK, sV, scr, b, h, 2 * wave, tid, wave);
 }
 
 // Measured and removed (round 3, git history: "attention: persistent 16-wave S=257 kernel"): ONE 1024-thread workgroup per CU walking its
@@ -497,9 +457,20 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_dh64_s257_kernel(const AttnPa
 // (init, four key blocks, class-query share, two barriers) is latency-bound; two subtiles per wave give it two independent chains to
 // interleave, one subtile per wave does not, and sixteen such waves per CU do not make up for it.
 
-}  // namespace
+// Which kernel a shape takes and how it is launched.  Pure: reads the shape and the two switches.  What the kernels rely on (their
+// `nq` ladders have no branch for more): the 4-wave kernel deals at most 3 subtiles to a wave — floor(ntile / 8) workgroups, but never
+// fewer than ceil(ntile / 12): ntile < 8 (nb + 1) <= 12 nb holds from nb = 2 on, and ONE workgroup left a wave 4 subtiles at ntile =
+// 13..15 (S = 193..240), which it then skipped — the 8-wave kernel at most 2 (ceil(ntile / 16)); tests/test_attn_dh64_plan_cpu.py sweeps both.
+AttnDh64Plan attn_dh64_plan(int B, int S, int H) {
+    static const int s257_on = medp_env_int("MEDP_ATTN_S257", 1);             // 0: the general kernel at S = 257 (A/B runs)
+    static const int w8_min_s = medp_env_int("MEDP_ATTN_W8_MIN_S", 512);      // 0 / huge: never the 8-wave kernel (A/B runs)
+    if (S == S257 && s257_on) return {ATTN_DH64_S257, B * H, 1, 1, 512, LDS_257, CR257};
+    const int ntile = (S + 15) / 16, crows = min(KC, (S + 31) / 32 * 32);      // 288 rows at S = 257: TWO workgroups fit a CU
+    if (w8_min_s > 0 && S >= w8_min_s) return {ATTN_DH64_W8, (ntile + 15) / 16, H, B, 512, 2 * crows * IMG_ROW, crows};
+    return {ATTN_DH64_W4, max(ntile / 8, (ntile + 11) / 12), H, B, 256, 2 * crows * IMG_ROW, crows};
+}
 
-static int g_s257_slots_override = 0;       // medp_dbg_attn_s257_slots (tests): pretend the device has this many resident slots
+}  // namespace
 
 static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int H, int ldq, int ldk,
                            int ldv, int ldo, float scale, void* stream) {
@@ -508,50 +479,18 @@ static int attn_fwd_launch(const void* q, const void* k, const void* v, void* o,
     MEDP_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0, "attn_fwd_dh64: row strides must keep 16-B alignment");
     MEDP_CHECK_ARG(B <= 65535 && H <= 65535, "attn_fwd_dh64: grid limit");
     MEDP_CHECK_ARG(scale > 0.f, "attn_fwd_dh64: scale must be positive (it is folded into the running max)");
-    AttnParams p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, B, S, H, ldq, ldk, ldv, ldo,
-                 scale * 1.4426950408889634f, 0, lse};
-    // S = 257 (224 x 224 images): the one-workgroup-per-(batch, head) kernel (MEDP_ATTN_S257=0: the general kernel, for A/B runs)
-    static const int s257_on = medp_env_int("MEDP_ATTN_S257", 1);
-    if (S == S257 && s257_on) {
-        MEDP_ONCE_PER_DEVICE({
-            hipFuncSetAttribute((const void*)attn_fwd_dh64_s257_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_257);
-            hipFuncSetAttribute((const void*)attn_fwd_dh64_s257_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_257);
-        });
-        // resident slots: 2 workgroups per CU (LDS).  Whole rounds of (b, h) as <2>; a remainder of at most half a round as <1> halves
-        // (MEDP_ATTN_S257_BALANCE=1 or medp_dbg_attn_s257_slots: the half-unit arrangement, kept for A/B runs and its test)
-        static const int dev_slots = [] { int dev = 0, cus = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); return 2 * cus; }();
-        const int slots = g_s257_slots_override > 0 ? g_s257_slots_override : dev_slots;
-        // Measured (B 64, H 12: 768 (b, h) on 512 slots): whole units only 32.2 us, whole + half units 37.8 us — a (b, h)'s cost is its 99 KB of
-        // loads, not its 16 subtiles of arithmetic, and a half unit loads all of K / V for half the queries.  Default: whole units.
-        static const int bal = medp_env_int("MEDP_ATTN_S257_BALANCE", 0);
-        const int n = B * H, rem = n % slots;
-        const bool halves = bal || g_s257_slots_override > 0;        // (the test hook plans halves on its pretended slots)
-        const int n_half = (halves && n > slots && rem > 0 && 2 * rem <= slots) ? rem : 0, n_whole = n - n_half;
-        attn_fwd_dh64_s257_kernel<2><<<n_whole, 512, LDS_257, (hipStream_t)stream>>>(p, 0);
-        if (n_half) attn_fwd_dh64_s257_kernel<1><<<2 * n_half, 512, LDS_257, (hipStream_t)stream>>>(p, n_whole);
-        MEDP_LAUNCH_CHECK("medp_attn_fwd_dh64(S=257)");
-        return 0;
-    }
-    p.crows = min(KC, (S + 31) / 32 * 32);
-    constexpr int LDS_MAX = 2 * KC * 128;
-    const int LDS = 2 * p.crows * 128;
+    const AttnDh64Plan pl = attn_dh64_plan(B, S, H);
+    const AttnParams p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, B, S, H, ldq, ldk, ldv, ldo,
+                       scale * 1.4426950408889634f, pl.crows, lse};
     MEDP_ONCE_PER_DEVICE({
-        hipFuncSetAttribute((const void*)attn_fwd_dh64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+        hipFuncSetAttribute((const void*)attn_fwd_dh64_s257_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_257);
+        hipFuncSetAttribute((const void*)attn_fwd_dh64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KC * IMG_ROW);
+        hipFuncSetAttribute((const void*)attn_fwd_dh64_w8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * KC * IMG_ROW);
     });
-    const int ntile = (S + 15) / 16;
-    static const int w8_min_s = medp_env_int("MEDP_ATTN_W8_MIN_S", 512);      // 0 / huge: never (A/B runs)
-    if (w8_min_s > 0 && S >= w8_min_s) {
-        MEDP_ONCE_PER_DEVICE({
-            hipFuncSetAttribute((const void*)attn_fwd_dh64_w8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-        });
-        dim3 grid8((ntile + 15) / 16, H, B);                   // ceil: every wave gets 1..2 subtiles (or none in the last workgroup)
-        attn_fwd_dh64_w8_kernel<<<grid8, 512, LDS, (hipStream_t)stream>>>(p);
-        MEDP_LAUNCH_CHECK("medp_attn_fwd_dh64(8 waves)");
-        return 0;
-    }
-    // floor(ntile/8) workgroups: every wave gets 1..3 subtiles (ntile < 8*(nb+1) <= 12*nb)
-    dim3 grid(ntile >= 8 ? ntile / 8 : 1, H, B);
-    attn_fwd_dh64_kernel<<<grid, 256, LDS, (hipStream_t)stream>>>(p);
+    const dim3 grid(pl.gx, pl.gy, pl.gz);
+    if (pl.kernel == ATTN_DH64_S257) attn_fwd_dh64_s257_kernel<<<grid, pl.threads, pl.lds, (hipStream_t)stream>>>(p, 0);
+    else if (pl.kernel == ATTN_DH64_W8) attn_fwd_dh64_w8_kernel<<<grid, pl.threads, pl.lds, (hipStream_t)stream>>>(p);
+    else attn_fwd_dh64_kernel<<<grid, pl.threads, pl.lds, (hipStream_t)stream>>>(p);
     MEDP_LAUNCH_CHECK("medp_attn_fwd_dh64");
     return 0;
 }
@@ -567,10 +506,20 @@ extern "C" int medp_attn_fwd_dh64_lse(const void* q, const void* k, const void* 
     return attn_fwd_launch(q, k, v, o, lse, B, S, H, ldq, ldk, ldv, ldo, scale, stream);
 }
 
-// Debug hook (NOT part of the C ABI in include/medp_hip.h; tests/test_gpu_kernels.py): resident-slot count the S = 257 launcher plans
-// with (0 = the device's own 2 x CUs), so that the half-unit kernel can be exercised at small B x H.  Returns the previous value.
-extern "C" int medp_dbg_attn_s257_slots(int slots) {
-    const int prev = g_s257_slots_override;
-    g_s257_slots_override = slots > 0 ? slots : 0;
-    return prev;
+// Debug hook (NOT part of the C ABI in include/medp_hip.h; tests/test_attn_dh64_plan_cpu.py): the plan of a shape, forward or backward,
+// without a device.  out[0..6] = kernel (ATTN_DH64_*), grid x, y, z, threads, dynamic LDS bytes, LDS rows per image; out[7] = the most
+// 16-row subtiles a wave receives and out[8] = the subtiles dealt over all waves of one (b, h) under the kernels' deal rule (S = 257
+// kernel: two patch subtiles per wave plus the class-query subtile, which the eight waves share).
+extern "C" int medp_dbg_attn_dh64_plan(int backward, int B, int S, int H, int* out) {
+    MEDP_CHECK_ARG(out && B > 0 && S > 0 && H > 0, "attn_dh64_plan: bad argument");
+    const AttnDh64Plan pl = backward ? attn_dh64_bwd_plan(B, S, H) : attn_dh64_plan(B, S, H);
+    const int ntile = (S + 15) / 16, nwave = pl.gx * (pl.threads / 64), s257 = pl.kernel == ATTN_DH64_S257;
+    int most = s257 ? 2 : 0, sum = s257 ? 17 : 0;
+    for (int gw = 0; gw < nwave && !s257; ++gw) {
+        const int nq = ntile / nwave + (gw < ntile % nwave ? 1 : 0);      // as the kernels compute it
+        most = max(most, nq), sum += nq;
+    }
+    const int vals[9] = {pl.kernel, pl.gx, pl.gy, pl.gz, pl.threads, pl.lds, pl.crows, most, sum};
+    for (int i = 0; i < 9; ++i) out[i] = vals[i];
+    return 0;
 }

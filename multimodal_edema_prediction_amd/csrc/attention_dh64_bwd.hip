@@ -12,15 +12,10 @@
 //                          P and dS (queries on rows, key on the lane) are the B operands of dV^T = dO^T P, dK^T = Q^T dS
 // The transposed A operands (K^T, dO^T, Q^T) come from the row-major images through ds_read_b64_tr_b16, exactly as V^T does
 // in the forward, so nothing is ever transposed in memory and P / dS never leave registers.
-#include "common.h"
+#include "attention_dh64_tile.h"
 #include "medp_hip.h"
 
 namespace {
-
-__device__ __attribute__((aligned(16))) uint32_t g_zero16_attnb[4] = {0, 0, 0, 0};
-
-constexpr int KC = 320;   // most rows per LDS chunk
-constexpr int NW = 2;     // most 16-row subtiles one wave owns
 
 struct BwdParams {
     const bf16_t *q, *k, *v, *dob;
@@ -31,24 +26,15 @@ struct BwdParams {
     int crows;
 };
 
-__device__ __forceinline__ bf16x8 pack8(const f32x4 a, const f32x4 b) {
-    union { bf16x8 v; uint32_t u[4]; } pk;
-    pk.u[0] = pack_bf2(a[0], a[1]);
-    pk.u[1] = pack_bf2(a[2], a[3]);
-    pk.u[2] = pack_bf2(b[0], b[1]);
-    pk.u[3] = pack_bf2(b[2], b[3]);
-    return pk.v;
-}
-
 template <bool DKV, int NWW>
 __device__ __forceinline__ void wave_body(const BwdParams& p, char* smem, int own0, int b, int h, int tid, int wave) {
     const int lane = tid & 63, fr = lane & 15, kq = lane >> 4;
     const int niter = p.crows >> 5;
     char* sX = smem;                              // dQ: K   | dK/dV: Q
-    char* sY = smem + p.crows * 128;              // dQ: V   | dK/dV: dO
-    float* sL = (float*)(smem + 2 * p.crows * 128);
+    char* sY = smem + p.crows * IMG_ROW;          // dQ: V   | dK/dV: dO
+    float* sL = (float*)(smem + 2 * p.crows * IMG_ROW);
     float* sD = sL + p.crows;
-    const bf16_t* zero = (const bf16_t*)g_zero16_attnb;
+    const bf16_t* zero = (const bf16_t*)g_zero16_attn;
     const size_t row0 = (size_t)b * p.S;
     const size_t st0 = ((size_t)b * p.H + h) * p.S;
     const bf16_t* gX = DKV ? p.q : p.k;           // image sources
@@ -87,14 +73,7 @@ __device__ __forceinline__ void wave_body(const BwdParams& p, char* smem, int ow
     for (int c0 = 0; c0 < p.S; c0 += KC) {
         const int nrows = min(KC, p.S - c0);
         if (c0 > 0) __syncthreads();
-        for (int i = 0; i < niter; ++i) {
-            const int qd = i * 256 + tid;
-            const int row = qd >> 3, ch = (qd & 7) ^ (row & 7);
-            const bool ok = row < nrows;
-            const size_t grow = row0 + c0 + row;
-            glds16(ok ? gX + grow * ldX + h * 64 + ch * 8 : zero, sX + (i * 256 + wave * 64) * 16);
-            glds16(ok ? gY + grow * ldY + h * 64 + ch * 8 : zero, sY + (i * 256 + wave * 64) * 16);
-        }
+        for (int i = 0; i < niter; ++i) img_stage_piece<256>(gX, ldX, gY, ldY, zero, sX, sY, row0 + c0, nrows, h, i, tid, wave);
         if (DKV) {
             for (int i = tid; i < p.crows; i += 256) {
                 const bool ok = i < nrows;
@@ -114,12 +93,9 @@ __device__ __forceinline__ void wave_body(const BwdParams& p, char* smem, int ow
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
                         const int r = kb * 64 + (2 * ks + t) * 16 + fr;
-                        const char* bx = sX + r * 128;
-                        const char* by = sY + r * 128;
-                        const bf16x8 x0 = *(const bf16x8*)(bx + (((0 + kq) ^ (r & 7)) << 4));
-                        const bf16x8 x1 = *(const bf16x8*)(bx + (((4 + kq) ^ (r & 7)) << 4));
-                        const bf16x8 y0 = *(const bf16x8*)(by + (((0 + kq) ^ (r & 7)) << 4));
-                        const bf16x8 y1 = *(const bf16x8*)(by + (((4 + kq) ^ (r & 7)) << 4));
+                        bf16x8 x0, x1, y0, y1;
+                        img_frag(sX, r, kq, x0, x1);
+                        img_frag(sY, r, kq, y0, y1);
 #pragma unroll
                         for (int w = 0; w < NWW; ++w) {
                             f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f}, d = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -163,14 +139,12 @@ __device__ __forceinline__ void wave_body(const BwdParams& p, char* smem, int ow
                     const int key1 = key0 + 16;
 #pragma unroll
                     for (int dt = 0; dt < 4; ++dt) {
-                        const int chunk = dt * 2 + (tr_p >> 1), off = (tr_p & 1) * 8;
-                        const int o0 = key0 * 128 + ((chunk ^ (key0 & 7)) << 4) + off;
-                        const int o1 = key1 * 128 + ((chunk ^ (key1 & 7)) << 4) + off;
-                        const bf16x8 xt = __builtin_shufflevector(lds_tr16(sX + o0), lds_tr16(sX + o1), 0, 1, 2, 3, 4, 5, 6, 7);
+                        const int o0 = (IMG_TR_TERMS(key0, dt, tr_p)), o1 = (IMG_TR_TERMS(key1, dt, tr_p));
+                        const bf16x8 xt = img_tr(sX, o0, o1);
 #pragma unroll
                         for (int w = 0; w < NWW; ++w) acc1[w][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xt, pS[w], acc1[w][dt], 0, 0, 0);
                         if (DKV) {
-                            const bf16x8 yt = __builtin_shufflevector(lds_tr16(sY + o0), lds_tr16(sY + o1), 0, 1, 2, 3, 4, 5, 6, 7);
+                            const bf16x8 yt = img_tr(sY, o0, o1);
 #pragma unroll
                             for (int w = 0; w < NWW; ++w) acc2[w][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(yt, pP[w], acc2[w][dt], 0, 0, 0);
                         }
@@ -208,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dh64_kernel(const BwdParams p
     const int b = blockIdx.z, h = blockIdx.y;
     const int ntile = (p.S + 15) >> 4, nwave = gridDim.x * 4, gw = blockIdx.x * 4 + wave;
     const int tbase = ntile / nwave, trem = ntile % nwave;
-    const int nw = tbase + (gw < trem ? 1 : 0);                 // subtiles of this wave (<= NW by the grid choice)
+    const int nw = tbase + (gw < trem ? 1 : 0);                 // subtiles of this wave (<= 2: attn_dh64_bwd_plan)
     const int own0 = (gw * tbase + min(gw, trem)) * 16;
     if (nw == 2) wave_body<DKV, 2>(p, smem, own0, b, h, tid, wave);
     else if (nw == 1) wave_body<DKV, 1>(p, smem, own0, b, h, tid, wave);
@@ -245,6 +219,13 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const float* __restr
 
 }  // namespace
 
+// Grid, LDS and image rows of the two backward launches (one rule: ceil(ntile / 8) workgroups of 4 waves, so that every wave owns 0..2
+// subtiles, which is all the kernel's `nw` ladder has branches for; the LDS holds the two images and crows floats each of L and D).
+AttnDh64Plan attn_dh64_bwd_plan(int B, int S, int H) {
+    const int ntile = (S + 15) / 16, crows = min(KC, (S + 31) / 32 * 32);
+    return {ATTN_DH64_BWD, (ntile + 7) / 8, H, B, 256, 2 * crows * IMG_ROW + 2 * crows * 4, crows};
+}
+
 extern "C" int medp_attn_bwd_dh64_prep(const float* dout, int lddout, const void* o_bf16, int ldo, void* dout_bf16, int lddob,
                                        float* dsum, int B, int S, int H, void* stream) {
     MEDP_CHECK_ARG(dout && o_bf16 && dout_bf16 && dsum, "attn_bwd_dh64_prep: null operand");
@@ -263,20 +244,18 @@ extern "C" int medp_attn_bwd_dh64(const void* q, const void* k, const void* v, i
     MEDP_CHECK_ARG(B > 0 && S > 0 && H > 0 && B <= 65535 && H <= 65535, "attn_bwd_dh64: bad shape B=%d S=%d H=%d", B, S, H);
     MEDP_CHECK_ARG(ldqkv % 8 == 0 && lddo % 8 == 0 && ldd % 4 == 0, "attn_bwd_dh64: row strides must keep 16-B alignment");
     MEDP_CHECK_ARG(scale > 0.f, "attn_bwd_dh64: scale must be positive");
-    BwdParams p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout_bf16, lse, dsum, dq, dk, dv,
-                B, S, H, ldqkv, lddo, ldd, scale, scale * 1.4426950408889634f, 0};
-    p.crows = min(KC, (S + 31) / 32 * 32);
-    constexpr int LDS_MAX = 2 * KC * 128 + 2 * KC * 4;
-    const int LDS = 2 * p.crows * 128 + 2 * p.crows * 4;
+    const AttnDh64Plan pl = attn_dh64_bwd_plan(B, S, H);
+    const BwdParams p{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)dout_bf16, lse, dsum, dq, dk, dv,
+                B, S, H, ldqkv, lddo, ldd, scale, scale * 1.4426950408889634f, pl.crows};
+    constexpr int LDS_MAX = 2 * KC * IMG_ROW + 2 * KC * 4;
     MEDP_ONCE_PER_DEVICE({
         hipFuncSetAttribute((const void*)attn_bwd_dh64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
         hipFuncSetAttribute((const void*)attn_bwd_dh64_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     });
-    const int ntile = (S + 15) / 16;
-    dim3 grid((ntile + 7) / 8, H, B);              // every wave owns 0..2 subtiles
-    attn_bwd_dh64_kernel<false><<<grid, 256, LDS, (hipStream_t)stream>>>(p);
+    const dim3 grid(pl.gx, pl.gy, pl.gz);
+    attn_bwd_dh64_kernel<false><<<grid, pl.threads, pl.lds, (hipStream_t)stream>>>(p);
     MEDP_LAUNCH_CHECK("medp_attn_bwd_dh64(dq)");
-    attn_bwd_dh64_kernel<true><<<grid, 256, LDS, (hipStream_t)stream>>>(p);
+    attn_bwd_dh64_kernel<true><<<grid, pl.threads, pl.lds, (hipStream_t)stream>>>(p);
     MEDP_LAUNCH_CHECK("medp_attn_bwd_dh64(dkv)");
     return 0;
 }

@@ -21,7 +21,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HAND_COUNTED = {
     "gemm_bf16_v6.hip": ["gemm_bf16_nt_v6_kernel"],
     "gemm_bf16_v7.hip": ["gemm_bf16_nt_v7_kernel"],
-    "attention_dh64.hip": ["attn_fwd_dh64_s257_kernel"],
+    "attention_dh64.hip": ["attn_fwd_dh64_s257_kernel"],          # one plain kernel (its LDS-image helpers: csrc/attention_dh64_tile.h)
 }
 
 
