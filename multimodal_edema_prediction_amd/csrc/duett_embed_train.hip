@@ -9,6 +9,7 @@
 //   load + v_readlane, so the FMAs take them as scalar operands.  Sums over rows are per-lane accumulators, combined across waves and
 //   row chunks in a fixed order: bitwise reproducible, no atomics.
 #include "common.h"
+#include "grouped_bn.h"
 #include "medp_hip.h"
 
 namespace {
@@ -56,11 +57,11 @@ __global__ __launch_bounds__(256) void gmlp_stats_partial_kernel(const float* __
     __syncthreads();
     if (rl == 0) {
         float* o = part + (((size_t)g * nchunk + chunk) * 2) * C;
-        o[c] = (red[0][0][c] + red[0][1][c]) + (red[0][2][c] + red[0][3][c]);
-        o[C + c] = (red[1][0][c] + red[1][1][c]) + (red[1][2][c] + red[1][3][c]);
+        o[c] = sum4_fixed(red[0][0][c], red[0][1][c], red[0][2][c], red[0][3][c]);
+        o[C + c] = sum4_fixed(red[1][0][c], red[1][1][c], red[1][2][c], red[1][3][c]);
     }
 }
-// chunks added in order; mean / biased variance saved for the backward; running statistics updated as gbn_running_kernel does
+// chunks added in order; mean / biased variance saved for the backward; running statistics updated in the same launch
 template <int KIN>
 __global__ __launch_bounds__(256) void gmlp_stats_final_kernel(const float* __restrict__ x, const float* __restrict__ W0, const float* __restrict__ b0,
                                                                const float* __restrict__ part, float* __restrict__ mean, float* __restrict__ var,
@@ -74,21 +75,10 @@ __global__ __launch_bounds__(256) void gmlp_stats_final_kernel(const float* __re
     for (int k = 0; k < KIN; ++k) p.w0[k] = W0[(size_t)i * KIN + k];
     p.b0 = b0[i];
     const float pivot = fmaxf(pre_act<KIN>(p, x + (size_t)g * R * KIN), 0.f);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < nchunk; ++k) {
-        const float* o = part + (((size_t)g * nchunk + k) * 2) * C;
-        s1 += o[c];
-        s2 += o[C + c];
-    }
-    const float m1 = s1 / (float)R;
-    const float mu = pivot + m1, v = fmaxf(s2 / (float)R - m1 * m1, 0.f);
-    mean[i] = mu;
-    var[i] = v;
-    if (rmean && rvar) {
-        rmean[i] = (1.f - momentum) * rmean[i] + momentum * mu;
-        rvar[i] = (1.f - momentum) * rvar[i] + momentum * v * ((float)R / (float)max(R - 1, 1));
-    }
+    float s1, s2;
+    bn_sum_stat_chunks(part, g, c, C, nchunk, &s1, &s2);
+    bn_finish_stats(s1, s2, pivot, R, &mean[i], &var[i]);
+    if (rmean && rvar) bn_running_update(&rmean[i], &rvar[i], mean[i], var[i], R, momentum);
 }
 
 // ---- forward, pass 2: out[r][:] = b1 + W1 BN(relu(W0 x[r] + b0)).  The group's parameters are broadcast out of LDS; a broadcast read
@@ -142,7 +132,7 @@ __global__ __launch_bounds__(OUT_THREADS) void gmlp_out_kernel(const float* __re
 #pragma unroll
             for (int k = 0; k < KIN; ++k) a += pv[k] * xr[j][k];
             a = fmaxf(a, 0.f);
-            hb[j] = (a - pv[KIN + 1]) * pv[KIN + 2] * pv[KIN + 3] + pv[KIN + 4];            // the expression of gbn_apply_kernel
+            hb[j] = bn_apply(a, pv[KIN + 1], pv[KIN + 2], pv[KIN + 3], pv[KIN + 4]);
         }
 #pragma unroll
         for (int n4 = 0; n4 < E / 4; ++n4) {
@@ -260,7 +250,7 @@ __global__ __launch_bounds__(256) void gmlp_bwd_sums_kernel(const float* __restr
         RS::row(smem, rl, xr, dn);
         const float a = fmaxf(pre_act<KIN>(st.p, xr), 0.f);
         const float xhat = (a - st.p.mu) * st.p.rs;
-        const float hb = xhat * st.p.bw + st.p.bb;
+        const float hb = bn_apply(a, st.p.mu, st.p.rs, st.p.bw, st.p.bb);
         float dhb = 0.f;
 #pragma unroll
         for (int n = 0; n < E; ++n) {
@@ -280,39 +270,13 @@ __global__ __launch_bounds__(256) void gmlp_bwd_sums_kernel(const float* __restr
     float* o = part + ((size_t)g * nchunk + chunk) * (E * C + 2 * C + E);
     for (int i = threadIdx.x; i < (E + 3) * C; i += 256) {
         const int q = i / C, c = i - q * C;
-        const float v = (red[0][q][c] + red[1][q][c]) + (red[2][q][c] + red[3][q][c]);
+        const float v = sum4_fixed(red[0][q][c], red[1][q][c], red[2][q][c], red[3][q][c]);
         if (q < E + 2) o[i] = v;                               // dW1 rows, s1, s2 keep the [q][c] layout
         else if (c < E) o[(E + 2) * C + c] = v;                // db1: lanes 0..E-1 carry it
     }
 }
-// chunks added in order, each block of the sum written where it belongs: dW1 [G][E][C] | d(bn bias) = s1 [G][C] | d(bn weight) = s2 [G][C] | db1 [G][E]
-template <int E>
-__global__ __launch_bounds__(256) void gmlp_bwd_sums_final_kernel(const float* __restrict__ part, float* __restrict__ dW1, float* __restrict__ dbn_b,
-                                                                  float* __restrict__ dbn_w, float* __restrict__ db1, int nchunk) {
-    constexpr int D = E * C + 2 * C + E;
-    const int g = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= D) return;
-    float a = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < nchunk; ++k) a += part[((size_t)g * nchunk + k) * D + i];
-    if (i < E * C) dW1[(size_t)g * E * C + i] = a;
-    else if (i < E * C + C) dbn_b[(size_t)g * C + (i - E * C)] = a;
-    else if (i < E * C + 2 * C) dbn_w[(size_t)g * C + (i - E * C - C)] = a;
-    else db1[(size_t)g * E + (i - E * C - 2 * C)] = a;
-}
-template <int KIN>
-__global__ __launch_bounds__(256) void gmlp_bwd_dx_final_kernel(const float* __restrict__ part, float* __restrict__ dW0, float* __restrict__ db0, int nchunk) {
-    constexpr int D = C * KIN + C;
-    const int g = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= D) return;
-    float a = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < nchunk; ++k) a += part[((size_t)g * nchunk + k) * D + i];
-    if (i < C * KIN) dW0[(size_t)g * C * KIN + i] = a;
-    else db0[(size_t)g * C + (i - C * KIN)] = a;
-}
+// chunk_sum (grouped_bn.h) adds the chunks in order, each block of the sum written where it belongs: dW1 [G][E][C] | d(bn bias) = s1 [G][C] |
+// d(bn weight) = s2 [G][C] | db1 [G][E]
 
 // pass 2: dpre = relu'(a) BN'(dhb);  dx[r][k] = sum_c dpre W0[c][k] (wave reduction);  per chunk  dW0[c][k] = sum_r dpre x[r][k],  db0[c] = sum_r dpre
 // s1 / s2 [G][C]: the finished BatchNorm sums of pass 1 (= the gradients of its bias / weight).  partial layout per (g, chunk): C*KIN (dW0) | C (db0)
@@ -346,9 +310,8 @@ __global__ __launch_bounds__(256) void gmlp_bwd_dx_kernel(const float* __restric
         float dhb = 0.f;
 #pragma unroll
         for (int n = 0; n < E; ++n) dhb += dn[n] * st.w1c[n];
-        float v = dhb;
-        if (batch_stats) v -= s1 / (float)R + (a - st.p.mu) * st.p.rs * s2 / (float)R;      // the expression of gbn_bwd_dx_kernel
-        const float da = st.p.bw * st.p.rs * v;
+        const float da = bn_dx(dhb, st.p.rs, R, batch_stats, [&] { return s1; }, [&] { return a - st.p.mu; }, [&] { return s2; },
+                               [&] { return st.p.bw; });
         const float dpre = a > 0.f ? da : 0.f;
         db0 += dpre;
 #pragma unroll
@@ -367,7 +330,7 @@ __global__ __launch_bounds__(256) void gmlp_bwd_dx_kernel(const float* __restric
     float* o = part + ((size_t)g * nchunk + chunk) * (C * KIN + C);
     for (int i = threadIdx.x; i < (KIN + 1) * C; i += 256) {
         const int q = i / C, c = i - q * C;
-        const float v = (red[0][q][c] + red[1][q][c]) + (red[2][q][c] + red[3][q][c]);
+        const float v = sum4_fixed(red[0][q][c], red[1][q][c], red[2][q][c], red[3][q][c]);
         if (q < KIN) o[c * KIN + q] = v;                       // dW0 [C][KIN]
         else o[C * KIN + c] = v;                               // db0
     }
@@ -402,8 +365,7 @@ extern "C" int medp_gmlp_fwd(const float* x, const float* W0, const float* b0, c
         MEDP_LAUNCH_CHECK("medp_gmlp_fwd(stats)");
     } else {
         MEDP_CHECK_ARG(running_mean && running_var, "gmlp_fwd: eval mode needs running statistics");
-        (void)hipMemcpyAsync(save_mean, running_mean, (size_t)G * C * 4, hipMemcpyDeviceToDevice, s);
-        (void)hipMemcpyAsync(save_var, running_var, (size_t)G * C * 4, hipMemcpyDeviceToDevice, s);
+        bn_save_running(save_mean, save_var, running_mean, running_var, (size_t)G * C, s);
     }
     gmlp_out_kernel<2, 24><<<dim3((R + OUT_THREADS * OUT_RPT - 1) / (OUT_THREADS * OUT_RPT), G), OUT_THREADS, 0, s>>>(x, W0, b0, bn_w, bn_b, save_mean, save_var, W1, b1,
                                                                                                                 out, R, eps);
@@ -421,15 +383,14 @@ extern "C" int medp_gmlp_bwd(const float* dout, const float* x, const float* W0,
     MEDP_CHECK_ARG(G <= 65535, "gmlp_bwd: at most 65535 groups");
     hipStream_t s = (hipStream_t)stream;
     const int nc = bw_chunks(R);
-    const int D1 = E * C + 2 * C + E, D0 = C * KIN + C;
     float* part1 = workspace;
-    float* part0 = part1 + (size_t)G * nc * D1;
+    float* part0 = part1 + (size_t)G * nc * (E * C + 2 * C + E);
     gmlp_bwd_sums_kernel<2, 24><<<dim3(nc, G), 256, 0, s>>>(dout, x, W0, b0, bn_w, bn_b, save_mean, save_var, W1, part1, R, eps);
-    gmlp_bwd_sums_final_kernel<24><<<dim3((D1 + 255) / 256, G), 256, 0, s>>>(part1, dW1, dbn_b, dbn_w, db1, nc);
+    chunk_sum(part1, G, nc, {{dW1, dbn_b, dbn_w, db1}, {E * C, C, C, E}}, s);
     MEDP_LAUNCH_CHECK("medp_gmlp_bwd(sums)");
     gmlp_bwd_dx_kernel<2, 24><<<dim3(nc, G), 256, 0, s>>>(dout, x, W0, b0, bn_w, bn_b, save_mean, save_var, W1, dbn_b, dbn_w, dx, part0, R, eps,
                                                           batch_stats);
-    gmlp_bwd_dx_final_kernel<2><<<dim3((D0 + 255) / 256, G), 256, 0, s>>>(part0, dW0, db0, nc);
+    chunk_sum(part0, G, nc, {{dW0, db0}, {C * KIN, C}}, s);
     MEDP_LAUNCH_CHECK("medp_gmlp_bwd(dx)");
     return 0;
 }

@@ -5,11 +5,12 @@
 // two-stage sums, no float atomics.  All fp32; FLOPs are negligible, the cost is HBM traffic and launch count.
 #include "common.h"
 #include "duett_cells.h"
+#include "grouped_bn.h"
 #include "medp_hip.h"
 
 namespace {
 
-// ---- grouped tiny linear: y[g][r][n] = b[g][n] + sum_k W[g][n][k] x[g][r][k]      (N*K <= 8192) ---------------------
+// ---- grouped tiny linear: y[g][r][n] = b[g][n] + sum_k W[g][n][k] x[g][r][k]      (N*(K+1) + N <= GLINEAR_MAX_FLOATS) ---
 constexpr int GLINEAR_MAX_FLOATS = 36000;     // weights (+ bias) of one group held in LDS: 144 KB of the CU's 160 KB
 // y[g][r][n] = b[g][n] + sum_k W[g][n][k] x[g][r][k].  ONE OUTPUT ELEMENT PER THREAD, consecutive threads = consecutive n of a row,
 // so every store instruction writes one contiguous span of y (the first form gave a thread a whole row: its 64 stores each
@@ -50,13 +51,12 @@ __global__ __launch_bounds__(256) void glinear_bwd_dx_kernel(const float* __rest
         dx[(size_t)g * total + idx] = a;
     }
 }
-// partial[g][chunk][n*K+k] = sum_{r in chunk} dy[r][n] x[r][k] ;  partial_b[g][chunk][n] = sum dy[r][n]
+// part[g][chunk][n*K+k] = sum_{r in chunk} dy[r][n] x[r][k] ;  part[g][chunk][N*K + n] = sum dy[r][n]   (dW | db: one chunk_sum finishes both)
 // The chunk's dy and x rows are staged in LDS with coalesced loads (they are contiguous spans), then every thread walks the rows
 // for its (n, k) outputs out of LDS — the first form read both operands straight from global memory inside the row loop, two
 // dependent loads per row and output (126 us per launch at cfg3).  Same summation order (ascending r): same values.
 __global__ __launch_bounds__(256) void glinear_bwd_dw_partial_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                                     float* __restrict__ pw, float* __restrict__ pb, int R, int K, int N,
-                                                                     int rows_per_chunk) {
+                                                                     float* __restrict__ part, int R, int K, int N, int rows_per_chunk) {
     extern __shared__ float sm[];            // [rows][N] dy, then [rows][K] x
     const int g = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x;
     const int r0 = chunk * rows_per_chunk, r1 = min(R, r0 + rows_per_chunk), nr = max(r1 - r0, 0);
@@ -67,26 +67,18 @@ __global__ __launch_bounds__(256) void glinear_bwd_dw_partial_kernel(const float
     for (int i = threadIdx.x; i < nr * N; i += 256) sdy[i] = dyg[i];
     for (int i = threadIdx.x; i < nr * K; i += 256) sx[i] = xg[i];
     __syncthreads();
+    float* o = part + ((size_t)g * nchunk + chunk) * ((size_t)N * K + N);
     for (int i = threadIdx.x; i < N * K; i += 256) {
         const int n = i / K, k = i % K;
         float a = 0.f;
         for (int r = 0; r < nr; ++r) a += sdy[r * N + n] * sx[r * K + k];
-        pw[((size_t)g * nchunk + chunk) * N * K + i] = a;
+        o[i] = a;
     }
     for (int n = threadIdx.x; n < N; n += 256) {
         float a = 0.f;
         for (int r = 0; r < nr; ++r) a += sdy[r * N + n];
-        pb[((size_t)g * nchunk + chunk) * N + n] = a;
+        o[N * K + n] = a;
     }
-}
-// out[g][i] = sum_chunk partial[g][chunk][i]
-__global__ __launch_bounds__(256) void sum_chunks_kernel(const float* __restrict__ partial, float* __restrict__ out, int nchunk, int D) {
-    const int g = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= D) return;
-    float a = 0.f;
-    for (int c = 0; c < nchunk; ++c) a += partial[((size_t)g * nchunk + c) * D + i];
-    out[(size_t)g * D + i] = a;
 }
 
 // ---- grouped BatchNorm over rows: x [G][R][C], statistics per (g, c) ------------------------------------------------
@@ -95,6 +87,7 @@ __global__ __launch_bounds__(256) void sum_chunks_kernel(const float* __restrict
 // in  var = S2/R - (S1/R)^2  for activations whose mean dwarfs their spread); (2) one thread per (g, c) adds the chunks in
 // order.  The first form ran ONE workgroup per group over all R rows (48 workgroups on 256 CUs, two dependent sweeps): 423 us
 // for a 75-MB operand at cfg3; the backward sums kernel had the same shape (427 us).
+// The formulas and the second stage are those of grouped_bn.h, shared with the fused MLP of duett_embed_train.hip.
 constexpr int GBN_RPC = 128;
 inline int gbn_chunks(int R) { return (R + GBN_RPC - 1) / GBN_RPC; }
 __global__ __launch_bounds__(256) void gbn_stats_partial_kernel(const float* __restrict__ x, float* __restrict__ part, int R, int C) {
@@ -117,8 +110,8 @@ __global__ __launch_bounds__(256) void gbn_stats_partial_kernel(const float* __r
     __syncthreads();
     if (rl == 0 && c < C) {
         float* o = part + (((size_t)g * nchunk + chunk) * 2) * C;
-        o[c] = (red[0][0][cl] + red[0][1][cl]) + (red[0][2][cl] + red[0][3][cl]);
-        o[C + c] = (red[1][0][cl] + red[1][1][cl]) + (red[1][2][cl] + red[1][3][cl]);
+        o[c] = sum4_fixed(red[0][0][cl], red[0][1][cl], red[0][2][cl], red[0][3][cl]);
+        o[C + c] = sum4_fixed(red[1][0][cl], red[1][1][cl], red[1][2][cl], red[1][3][cl]);
     }
 }
 __global__ __launch_bounds__(256) void gbn_stats_final_kernel(const float* __restrict__ x, const float* __restrict__ part, float* __restrict__ mean,
@@ -126,23 +119,15 @@ __global__ __launch_bounds__(256) void gbn_stats_final_kernel(const float* __res
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= G * C) return;
     const int g = i / C, c = i - g * C;
-    float s1 = 0.f, s2 = 0.f;
-    for (int k = 0; k < nchunk; ++k) {
-        const float* o = part + (((size_t)g * nchunk + k) * 2) * C;
-        s1 += o[c];
-        s2 += o[C + c];
-    }
-    const float m1 = s1 / (float)R;
-    mean[i] = x[(size_t)g * R * C + c] + m1;
-    var[i] = fmaxf(s2 / (float)R - m1 * m1, 0.f);             // biased
+    float s1, s2;
+    bn_sum_stat_chunks(part, g, c, C, nchunk, &s1, &s2);
+    bn_finish_stats(s1, s2, x[(size_t)g * R * C + c], R, &mean[i], &var[i]);
 }
-// running = (1-m)*running + m*batch  (unbiased variance), num_batches_tracked handled by the caller
 __global__ __launch_bounds__(256) void gbn_running_kernel(const float* __restrict__ mean, const float* __restrict__ var, float* __restrict__ rmean,
                                                           float* __restrict__ rvar, int n, int R, float momentum) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    rmean[i] = (1.f - momentum) * rmean[i] + momentum * mean[i];
-    rvar[i] = (1.f - momentum) * rvar[i] + momentum * var[i] * ((float)R / (float)max(R - 1, 1));
+    bn_running_update(&rmean[i], &rvar[i], mean[i], var[i], R, momentum);
 }
 __global__ __launch_bounds__(256) void gbn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ var,
                                                         const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ y,
@@ -151,10 +136,10 @@ __global__ __launch_bounds__(256) void gbn_apply_kernel(const float* __restrict_
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const int c = (int)(i % C), g = (int)(i / ((size_t)R * C));
         const int gc = g * C + c;
-        y[i] = (x[i] - mean[gc]) * rsqrtf(var[gc] + eps) * w[gc] + b[gc];
+        y[i] = bn_apply(x[i], mean[gc], rsqrtf(var[gc] + eps), w[gc], b[gc]);
     }
 }
-// sums for backward: s1[g][c] = sum_r dy ; s2[g][c] = sum_r dy * xhat — per chunk of rows, then added in order (see above)
+// sums for backward: s1[g][c] = sum_r dy ; s2[g][c] = sum_r dy * xhat — per chunk of rows, then added in order (chunk_sum)
 __global__ __launch_bounds__(256) void gbn_bwd_sums_partial_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                    const float* __restrict__ mean, const float* __restrict__ var,
                                                                    float* __restrict__ part, int R, int C, float eps) {
@@ -176,25 +161,10 @@ __global__ __launch_bounds__(256) void gbn_bwd_sums_partial_kernel(const float* 
     __syncthreads();
     if (rl == 0 && c < C) {
         float* o = part + (((size_t)g * nchunk + chunk) * 2) * C;
-        o[c] = (red[0][0][cl] + red[0][1][cl]) + (red[0][2][cl] + red[0][3][cl]);
-        o[C + c] = (red[1][0][cl] + red[1][1][cl]) + (red[1][2][cl] + red[1][3][cl]);
+        o[c] = sum4_fixed(red[0][0][cl], red[0][1][cl], red[0][2][cl], red[0][3][cl]);
+        o[C + c] = sum4_fixed(red[1][0][cl], red[1][1][cl], red[1][2][cl], red[1][3][cl]);
     }
 }
-__global__ __launch_bounds__(256) void gbn_bwd_sums_final_kernel(const float* __restrict__ part, float* __restrict__ s1, float* __restrict__ s2,
-                                                                 int G, int C, int nchunk) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= G * C) return;
-    const int g = i / C, c = i - g * C;
-    float a = 0.f, q = 0.f;
-    for (int k = 0; k < nchunk; ++k) {
-        const float* o = part + (((size_t)g * nchunk + k) * 2) * C;
-        a += o[c];
-        q += o[C + c];
-    }
-    s1[i] = a;
-    s2[i] = q;
-}
-// train: dx = w*rstd*(dy - s1/R - xhat*s2/R) ; eval (batch_stats == 0): dx = w*rstd*dy
 __global__ __launch_bounds__(256) void gbn_bwd_dx_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
                                                          const float* __restrict__ var, const float* __restrict__ w, const float* __restrict__ s1,
                                                          const float* __restrict__ s2, float* __restrict__ dx, int G, int R, int C, float eps,
@@ -204,9 +174,8 @@ __global__ __launch_bounds__(256) void gbn_bwd_dx_kernel(const float* __restrict
         const int c = (int)(i % C), g = (int)(i / ((size_t)R * C));
         const int gc = g * C + c;
         const float rs = rsqrtf(var[gc] + eps);
-        float v = dy[i];
-        if (batch_stats) v -= s1[gc] / (float)R + (x[i] - mean[gc]) * rs * s2[gc] / (float)R;
-        dx[i] = w[gc] * rs * v;
+        dx[i] = bn_dx(dy[i], rs, R, batch_stats, [&] { return s1[gc]; }, [&] { return x[i] - mean[gc]; }, [&] { return s2[gc]; },
+                      [&] { return w[gc]; });
     }
 }
 
@@ -262,7 +231,7 @@ __global__ __launch_bounds__(256) void embed_inputs_bwd_kernel(const float* __re
     }
     __syncthreads();
     if (threadIdx.x < nrows_table)
-        partial[(size_t)blockIdx.x * nrows_table + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+        partial[(size_t)blockIdx.x * nrows_table + threadIdx.x] = sum4_fixed(red[0][threadIdx.x], red[1][threadIdx.x], red[2][threadIdx.x], red[3][threadIdx.x]);
 }
 
 // ---- psi assembly (model :53-66) and its backward -------------------------------------------------------------------------
@@ -363,7 +332,7 @@ __global__ __launch_bounds__(256) void axis_swap_add_kernel(const float* __restr
         *(float4*)(out + i * 4) = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
     }
 }
-// out = a + b  (b broadcast over the leading batch dim when b_bs == 0)
+// out = a + b  (b broadcast over the leading batch dim when bcast != 0)
 __global__ __launch_bounds__(256) void add_bcast_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, size_t per_batch,
                                                         int B, int bcast) {
     const size_t n = per_batch * B;
@@ -417,16 +386,13 @@ extern "C" int medp_glinear_bwd(const float* dy, const float* x, const float* W,
         const int nc = dw_chunks(R, K, N);
         MEDP_CHECK_ARG(nc > 0, "glinear_bwd: one row of dy and x (N + K floats) must fit LDS");
         const int rpc = (R + nc - 1) / nc;
-        float* pw = workspace;
-        float* pb = workspace + (size_t)G * nc * N * K;
         MEDP_CHECK_ARG((size_t)rpc * (N + K) * 4 <= GLINEAR_DW_LDS_BYTES, "glinear_bwd: rows-per-chunk x (N + K) floats must fit LDS");
         MEDP_ONCE_PER_DEVICE({
             (void)hipFuncSetAttribute((const void*)glinear_bwd_dw_partial_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GLINEAR_DW_LDS_BYTES);
         });
-        glinear_bwd_dw_partial_kernel<<<dim3(nc, G), 256, (size_t)rpc * (N + K) * 4, s>>>(dy, x, pw, pb, R, K, N, rpc);
+        glinear_bwd_dw_partial_kernel<<<dim3(nc, G), 256, (size_t)rpc * (N + K) * 4, s>>>(dy, x, workspace, R, K, N, rpc);
         MEDP_LAUNCH_CHECK("medp_glinear_bwd(partial)");
-        sum_chunks_kernel<<<dim3((N * K + 255) / 256, G), 256, 0, s>>>(pw, dW, nc, N * K);
-        sum_chunks_kernel<<<dim3((N + 255) / 256, G), 256, 0, s>>>(pb, db, nc, N);
+        chunk_sum(workspace, G, nc, {{dW, db}, {N * K, N}}, s);
         MEDP_LAUNCH_CHECK("medp_glinear_bwd(final)");
     }
     return 0;
@@ -452,8 +418,7 @@ extern "C" int medp_gbn_fwd(const float* x, const float* w, const float* b, floa
         }
     } else {
         MEDP_CHECK_ARG(running_mean && running_var, "gbn_fwd: eval mode needs running statistics");
-        hipMemcpyAsync(save_mean, running_mean, (size_t)G * C * 4, hipMemcpyDeviceToDevice, s);
-        hipMemcpyAsync(save_var, running_var, (size_t)G * C * 4, hipMemcpyDeviceToDevice, s);
+        bn_save_running(save_mean, save_var, running_mean, running_var, (size_t)G * C, s);
     }
     gbn_apply_kernel<<<grid_for((size_t)G * R * C), 256, 0, s>>>(x, save_mean, save_var, w, b, y, G, R, C, eps);
     MEDP_LAUNCH_CHECK("medp_gbn_fwd(apply)");
@@ -465,7 +430,7 @@ extern "C" int medp_gbn_bwd(const float* dy, const float* x, const float* w, con
     hipStream_t s = (hipStream_t)stream;
     const int nc = gbn_chunks(R);
     gbn_bwd_sums_partial_kernel<<<dim3(nc, G, (C + 63) / 64), 256, 0, s>>>(dy, x, save_mean, save_var, workspace, R, C, eps);
-    gbn_bwd_sums_final_kernel<<<(G * C + 255) / 256, 256, 0, s>>>(workspace, db, dw, G, C, nc);
+    chunk_sum(workspace, G, nc, {{db, dw}, {C, C}}, s);
     MEDP_LAUNCH_CHECK("medp_gbn_bwd(sums)");
     gbn_bwd_dx_kernel<<<grid_for((size_t)G * R * C), 256, 0, s>>>(dy, x, save_mean, save_var, w, db, dw, dx, G, R, C, eps, batch_stats);
     MEDP_LAUNCH_CHECK("medp_gbn_bwd(dx)");

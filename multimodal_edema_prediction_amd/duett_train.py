@@ -6,14 +6,28 @@ operands and for autograd bookkeeping only.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import autograd_ops as A
 from . import functional as Fn
 from .abi import check, lib, ptr, stream
 
+
+def _switch(name):
+    """Environment switch MEDP_DUETT_<name>: on unless set to something other than "1" (read at import into attributes tests assign to; FUSED_SWAP per call)."""
+    return os.environ.get("MEDP_DUETT_" + name, "1") == "1"
+
+
 F32, BF16 = torch.float32, torch.bfloat16
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
+_FUSED_GMLP, _FOLD_RESIDUAL_ADD, _MFMA_ATTN, _FUSED_NODES = map(_switch, ("FUSED_GMLP", "FOLD_RESIDUAL_ADD", "TRAIN_MFMA_ATTN", "FUSED_NODES"))
+
+
+def _bn_buffers(G, C, ws_floats, device):
+    """(saved mean [G, C], saved variance [G, C], workspace of ws_floats floats or None) of a grouped BatchNorm forward"""
+    return [None if n is None else torch.empty(n, dtype=F32, device=device) for n in ((G, C), (G, C), ws_floats)]
 
 
 # ------------------------------------------------------------------------------------------------ grouped tiny layers
@@ -70,9 +84,7 @@ class GBatchNormFn(torch.autograd.Function):
         x, w, b = x.contiguous(), w.contiguous(), b.contiguous()
         G, R, C = x.shape
         y = torch.empty_like(x)
-        sm = torch.empty((G, C), dtype=F32, device=x.device)
-        sv = torch.empty((G, C), dtype=F32, device=x.device)
-        ws = torch.empty(lib().medp_gbn_workspace_bytes(G, R, C) // 4, dtype=F32, device=x.device) if batch_stats else None
+        sm, sv, ws = _bn_buffers(G, C, lib().medp_gbn_workspace_bytes(G, R, C) // 4 if batch_stats else None, x.device)
         check(lib().medp_gbn_fwd(ptr(x), ptr(w), ptr(b), ptr(rmean), ptr(rvar), ptr(y), ptr(sm), ptr(sv), G, R, C, BN_EPS, BN_MOMENTUM,
                                  int(batch_stats), ptr(ws), stream()), "gbn_fwd")
         ctx.save_for_backward(x, w, sm, sv)
@@ -102,9 +114,7 @@ class GroupMlpFn(torch.autograd.Function):
         G, R, KIN = x.shape
         Ch, E = W0.shape[1], W1.shape[1]
         out = torch.empty((G, R, E), dtype=F32, device=x.device)
-        sm = torch.empty((G, Ch), dtype=F32, device=x.device)
-        sv = torch.empty((G, Ch), dtype=F32, device=x.device)
-        ws = torch.empty(lib().medp_gmlp_workspace_bytes(G, R, KIN, Ch, E) // 4, dtype=F32, device=x.device)
+        sm, sv, ws = _bn_buffers(G, Ch, lib().medp_gmlp_workspace_bytes(G, R, KIN, Ch, E) // 4, x.device)
         check(lib().medp_gmlp_fwd(ptr(x), ptr(W0), ptr(b0), ptr(bn_w), ptr(bn_b), ptr(rmean), ptr(rvar), ptr(W1), ptr(b1), ptr(out), ptr(sm),
                                   ptr(sv), G, R, KIN, Ch, E, BN_EPS, BN_MOMENTUM, int(batch_stats), ptr(ws), stream()), "gmlp_fwd")
         ctx.save_for_backward(x, W0, b0, bn_w, bn_b, sm, sv, W1)
@@ -124,9 +134,6 @@ class GroupMlpFn(torch.autograd.Function):
         check(lib().medp_gmlp_bwd(ptr(d), ptr(x), ptr(W0), ptr(b0), ptr(bn_w), ptr(bn_b), ptr(sm), ptr(sv), ptr(W1), ptr(dx), ptr(dW0), ptr(db0),
                                   ptr(dbw), ptr(dbb), ptr(dW1), ptr(db1), G, R, KIN, Ch, E, BN_EPS, int(ctx.batch_stats), ptr(ws), stream()), "gmlp_bwd")
         return dx, dW0, db0, dbw, dbb, None, None, dW1, db1, None
-
-
-_FUSED_GMLP = __import__("os").environ.get("MEDP_DUETT_FUSED_GMLP", "1") == "1"
 
 
 class EmbedInputsFn(torch.autograd.Function):
@@ -297,10 +304,6 @@ class ResidualScaleNormFn(torch.autograd.Function):
         return dx.view_as(x), dg, None
 
 
-_FOLD_RESIDUAL_ADD = __import__("os").environ.get("MEDP_DUETT_FOLD_RESIDUAL_ADD", "1") == "1"
-_MFMA_ATTN = __import__("os").environ.get("MEDP_DUETT_TRAIN_MFMA_ATTN", "1") == "1"
-
-
 class SelfAttnQKVFn(torch.autograd.Function):
     """qkv [B, N, 3*H*dh] (q | k | v column blocks) -> [B, N, H*dh]; dense softmax, dropout on the probabilities.
     bf16 mode: the MFMA kernels of csrc/attention_dh16.hip (head dim <= 16, N <= 272); fp32 kernel mode or other shapes: the
@@ -341,9 +344,6 @@ class SelfAttnQKVFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------ fused halves of an encoder block
-_FUSED_NODES = __import__("os").environ.get("MEDP_DUETT_FUSED_NODES", "1") == "1"
-
-
 def _scalenorm_bwd_join(dh, x, g, rn, d_pass):
     """(d_pass + d ScaleNorm(x) / dx applied to dh, dg [1]): the residual join of a pre-norm half in the backward as ONE pass, out of place —
     `d_pass` (the gradient of the half's output, which the residual hands straight through) is only read."""
@@ -472,6 +472,15 @@ def _bind_stacked_bn(model):
     return model._bn_stack
 
 
+def _mlp_operands(mlp, bn_at, lin1_at, running=None):
+    """The operands (lin0_w, lin0_b, bn_w, bn_b, rm, rv, lin1_w, lin1_b) of `_mlp_bn` from `simple_mlp` modules ([0] Linear, [bn_at] BatchNormLastDim,
+    [lin1_at] Linear or None: no last Linear): one nn.Sequential is group 0, V of them are stacked (`running`: their stacked statistics)."""
+    group = (lambda f: f(mlp).unsqueeze(0)) if isinstance(mlp, torch.nn.Sequential) else (lambda f: torch.stack([f(m) for m in mlp]))
+    at = lambda i, name: group(lambda m: getattr(m[i].batch_norm if i == bn_at else m[i], name))
+    return [at(0, "weight"), at(0, "bias"), at(bn_at, "weight"), at(bn_at, "bias"), *(running or (at(bn_at, "running_mean"), at(bn_at, "running_var"))),
+            *((None, None) if lin1_at is None else (at(lin1_at, "weight"), at(lin1_at, "bias")))]
+
+
 def _mlp_bn(x, lin0_w, lin0_b, bn_w, bn_b, rm, rv, lin1_w, lin1_b, act_mode, batch_stats):
     if (_FUSED_GMLP and lin1_w is not None and act_mode == 0
             and lib().medp_gmlp_supported(x.shape[-1], lin0_w.shape[1], lin1_w.shape[1]) == 1):
@@ -518,38 +527,28 @@ def encode_training(model, x):
     if T != model.masked_transform_timesteps:
         raise ValueError(f"this backbone was built for n_timesteps={model.masked_transform_timesteps}, got T={T}")
     bs = bool(model.training)                                           # BatchNorm: batch statistics in train(), running in eval()
-    el = model.embedding_layers
     rm, rv, nbt = _bind_stacked_bn(model)
     # per-variable MLPs as ONE grouped pass (group = variable)                                  (model :45-55)
     xin = EmbedInputsFn.apply(xs_feats, model.n_obs_embedding.weight)
-    var_out = _mlp_bn(xin, torch.stack([m[0].weight for m in el]), torch.stack([m[0].bias for m in el]),
-                      torch.stack([m[3].batch_norm.weight for m in el]), torch.stack([m[3].batch_norm.bias for m in el]), rm, rv,
-                      torch.stack([m[4].weight for m in el]), torch.stack([m[4].bias for m in el]), 0, bs)
-    te = model.tab_encoder                                                                     # (model :57)
-    tbn = te[3].batch_norm
-    tab_out = _mlp_bn(xs_static.unsqueeze(0), te[0].weight.unsqueeze(0), te[0].bias.unsqueeze(0), tbn.weight.unsqueeze(0),
-                      tbn.bias.unsqueeze(0), tbn.running_mean.unsqueeze(0), tbn.running_var.unsqueeze(0), te[4].weight.unsqueeze(0),
-                      te[4].bias.unsqueeze(0), 0, bs)[0]
+    var_out = _mlp_bn(xin, *_mlp_operands(model.embedding_layers, 3, 4, [rm, rv]), 0, bs)
+    tab_out = _mlp_bn(xs_static.unsqueeze(0), *_mlp_operands(model.tab_encoder, 3, 4), 0, bs)[0]       # (model :57)
     psi = PsiAssembleFn.apply(xs_feats, var_out, tab_out, model.special_embeddings.weight)      # (model :53-66)
     # time embedding: Linear(1,h) -> tanh -> BN -> Linear(h, tt) ; hidden padded to a multiple of 8 for the MFMA GEMM   (model :67-69)
     tm = model.full_time_embedding
-    mbn = tm[2].batch_norm
-    hb = _mlp_bn(xs_times.reshape(1, B * T, 1), tm[0].weight.unsqueeze(0), tm[0].bias.unsqueeze(0), mbn.weight.unsqueeze(0),
-                 mbn.bias.unsqueeze(0), mbn.running_mean.unsqueeze(0), mbn.running_var.unsqueeze(0), None, None, 1, bs)[0]   # [B*T, h]
-    Hd = hb.shape[1]
-    pad = (-Hd) % 8
+    hb = _mlp_bn(xs_times.reshape(1, B * T, 1), *_mlp_operands(tm, 2, None), 1, bs)[0]          # [B*T, h]
+    pad = (-hb.shape[1]) % 8
     hb_p = torch.cat([hb, hb.new_zeros(hb.shape[0], pad)], 1) if pad else hb
     w3_p = torch.cat([tm[3].weight, tm[3].weight.new_zeros(tm[3].weight.shape[0], pad)], 1) if pad else tm[3].weight
     tt = E * (V + 1)
     temb = A.linear(hb_p, w3_p, tm[3].bias).view(B, T, tt)
-    fused_swap = __import__("os").environ.get("MEDP_DUETT_FUSED_SWAP", "1") == "1"
+    fused_swap = _switch("FUSED_SWAP")                    # read at call time
     if not fused_swap:
         time_emb = torch.cat([temb, model.full_rep_embedding.weight.view(1, 1, -1).expand(B, -1, -1)], 1)     # [B, T+1, tt]
     if bs:
         with torch.no_grad():
             nbt += 1                                      # all V per-variable counters at once (views of one stacked buffer)
-            tbn.num_batches_tracked += 1
-            mbn.num_batches_tracked += 1
+            model.tab_encoder[3].batch_norm.num_batches_tracked += 1
+            tm[2].batch_norm.num_batches_tracked += 1
     seed = A.next_seed() if (model.training and model.transformer_dropout > 0) else 0
     T1, V1 = T + 1, V + 1
     for l, (ev, tv) in enumerate(zip(model.event_transformers, model.time_transformers)):
