@@ -17,51 +17,54 @@ F32, BF16 = torch.float32, torch.bfloat16
 # ---------------------------------------------------------------------------------------------- weight caches
 from torch.utils.weak import WeakIdKeyDictionary
 
-# keyed by the OWNING tensor object (the nn.Parameter; for a view such as in_proj_weight[:d], its base), so an entry dies
-# with its parameter and a recycled device address can never alias a stale copy; validated by the version counter
+# owner -> {(kind, offset, shape, stride): (versions, value, partners)}.  The owner is the OWNING tensor object (the nn.Parameter;
+# for a view such as in_proj_weight[:d], its base), so an entry dies with its parameter and a recycled device address can never
+# alias a stale copy; the view signature keeps a view and its parameter apart.  An operand made of SEVERAL tensors (to_q | to_k |
+# to_v stacked by rows) is filed under the first one and is valid while every member is the same object at the same version; a
+# single weight is a group of one.  `_fetch` and `_store` are the only code that knows this layout.
 _W_CACHE = WeakIdKeyDictionary()
 
 
-def _cached(t: torch.Tensor, kind: str, make):
-    base = t._base if t._base is not None else t
-    sub = (t.storage_offset(), tuple(t.shape), tuple(t.stride()), kind)
-    ver = t._version
-    slot = _W_CACHE.get(base)
-    if slot is None:
-        slot = {}
-        _W_CACHE[base] = slot
-    hit = slot.get(sub)
-    if hit is not None and hit[0] == ver:
+def _entry_key(ts, kind):
+    t = ts[0]
+    return (t._base if t._base is not None else t), (kind, t.storage_offset(), tuple(t.shape), tuple(t.stride()))
+
+
+def _fetch(ts, kind: str):
+    """The cached `kind` operand of the tensors `ts`, or None when there is none for these objects at these versions."""
+    owner, key = _entry_key(ts, kind)
+    slot = _W_CACHE.get(owner)
+    hit = slot.get(key) if slot is not None else None
+    if (hit is not None and hit[0] == tuple(t._version for t in ts) and len(hit[2]) == len(ts) - 1
+            and all(a is b for a, b in zip(hit[2], ts[1:]))):
         return hit[1]
-    val = make(t.detach())
-    slot[sub] = (ver, val)
+    return None
+
+
+def _store(ts, kind: str, val):
+    """File `val` as the `kind` operand of `ts` at their current versions."""
+    owner, key = _entry_key(ts, kind)
+    slot = _W_CACHE.get(owner)
+    if slot is None:
+        slot = _W_CACHE[owner] = {}
+    slot[key] = (tuple(t._version for t in ts), val, tuple(ts[1:]))
     return val
 
 
-def _seed(t: torch.Tensor, kind: str, val: torch.Tensor) -> None:
-    """Put `val` into the cache as the `kind` operand of `t` at its current version (WeightOperandPool.refresh)."""
-    base = t._base if t._base is not None else t
-    slot = _W_CACHE.get(base)
-    if slot is None:
-        slot = {}
-        _W_CACHE[base] = slot
-    slot[(t.storage_offset(), tuple(t.shape), tuple(t.stride()), kind)] = (t._version, val)
+def live_operands() -> list:
+    """Every cached operand tensor (graph_step keeps them alive for as long as a captured graph points at them)."""
+    return [entry[1] for slot in _W_CACHE.values() for entry in slot.values()]
+
+
+def _cached(t: torch.Tensor, kind: str, make):
+    val = _fetch((t,), kind)
+    return val if val is not None else _store((t,), kind, make(t.detach()))
 
 
 def _cached_group(ts, kind: str, make):
-    """`_cached` for an operand made of SEVERAL tensors (to_q | to_k | to_v stacked by rows): filed under the first one, valid while
-    every member is the same object at the same version."""
-    slot = _W_CACHE.get(ts[0])
-    if slot is None:
-        slot = {}
-        _W_CACHE[ts[0]] = slot
-    vers = tuple(t._version for t in ts)
-    hit = slot.get(kind)
-    if hit is not None and hit[0] == vers and len(hit[2]) == len(ts) - 1 and all(a is b for a, b in zip(hit[2], ts[1:])):
-        return hit[1]
-    val = make([t.detach() for t in ts])
-    slot[kind] = (vers, val, tuple(ts[1:]))
-    return val
+    """`_cached` for an operand made of several tensors."""
+    val = _fetch(ts, kind)
+    return val if val is not None else _store(ts, kind, make([t.detach() for t in ts]))
 
 
 # while graph_step records a warm-up step: every (weights, kind) a trainable weight's operand was asked for, in order
@@ -169,24 +172,11 @@ class WeightOperandPool:
         check(lib().medp_weight_operands_multi(ptr(self._jobs), ptr(self._blk_job), ptr(self._blk_tile), self.n_blocks, stream()),
               "weight_operands_multi")
         for ws, plain, tr in self._groups:
-            if len(ws) == 1:
-                if plain is not None:
-                    _seed(ws[0], "bf16", plain)
-                if tr is not None:
-                    _seed(ws[0], "t_bf16", tr)
-            else:
-                slot = _W_CACHE.get(ws[0])
-                if slot is None:
-                    slot = {}
-                    _W_CACHE[ws[0]] = slot
-                vers = tuple(w._version for w in ws)
-                if plain is not None:
-                    slot["cat_bf16"] = (vers, plain, tuple(ws[1:]))
-                if tr is not None:
-                    slot["cat_t_bf16"] = (vers, tr, tuple(ws[1:]))
-
-
-_SEED_STATE = {"n": 0}
+            cat = "cat_" if len(ws) > 1 else ""                # the kinds weight_bf16 / weights_cat_bf16 (and _t_) ask for
+            if plain is not None:
+                _store(ws, cat + "bf16", plain)
+            if tr is not None:
+                _store(ws, cat + "t_bf16", tr)
 
 
 def next_seed() -> int:
@@ -195,37 +185,43 @@ def next_seed() -> int:
 
 
 # ---------------------------------------------------------------------------------------------- Linear
+def _input_operand(x):
+    """Forward prelude of the Linear family: x [..., K] fp32 or bf16 -> its GEMM operand as [M, K]."""
+    if Fn.precision() == "fp32" and x.dtype == BF16:
+        x = x.float()                                         # bf16 tokens of a frozen bf16 encoder entering an fp32-mode head
+    xb = x if x.dtype == BF16 else Fn.operand(x.contiguous())
+    return xb.reshape(-1, xb.shape[-1])
+
+
+def _weight_grad(dy2, dyb, x2, K):
+    """dW [N, K] = dY^T X from dY fp32 [M, N], its GEMM operand `dyb` and the saved operand x2 [M, K]."""
+    if dy2.shape[1] % 8 == 0 and K % 8 == 0 and x2.stride(0) % 8 == 0:
+        return Fn.gemm_tn(dyb, x2)                            # transposing LDS reads + split-m: no dY^T / X^T passes
+    dyt, xt = Fn.operand_t(dy2), Fn.operand_t(x2)             # [N, Mpad], [K, Mpad]
+    return Fn.gemm(dyt, xt, out_dtype=F32, k=dyt.shape[1])
+
+
 class LinearFn(torch.autograd.Function):
     """y = x W^T (+ b) (+ residual).  x: [..., K] fp32 or bf16; W: [N, K] fp32; y fp32."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, residual):
-        fp32 = Fn.precision() == "fp32"
-        if fp32 and x.dtype == BF16:
-            x = x.float()                                     # bf16 tokens of a frozen bf16 encoder entering an fp32-mode head
-        xb = x if x.dtype == BF16 else Fn.operand(x.contiguous())
-        x2 = xb.reshape(-1, xb.shape[-1])
+        x2 = _input_operand(x)
         N = weight.shape[0]
+        ctx.x_shape, ctx.has_bias, ctx.has_res = x.shape, bias is not None, residual is not None
         if N % 4:                                             # e.g. the 7-label linear probe: pad the weight rows, slice the result
             Np = (N + 3) // 4 * 4
-            wpad = _cached(weight, "f32_rowpad" if fp32 else "bf16_rowpad",
+            wpad = _cached(weight, "f32_rowpad" if Fn.precision() == "fp32" else "bf16_rowpad",
                            lambda t: Fn.operand(torch.cat([t, t.new_zeros(Np - N, t.shape[1])]).contiguous()))
             bpad = torch.cat([bias.detach(), bias.new_zeros(Np - N)]) if bias is not None else None
             y = Fn.gemm(x2, wpad, bias=bpad, out_dtype=F32, k=weight.shape[1])[:, :N].contiguous()
             if residual is not None:
                 raise ValueError("LinearFn: residual with N % 4 != 0 is not supported")
-            ctx.save_for_backward(x2, weight)
-            ctx.x_shape, ctx.has_bias, ctx.has_res = x.shape, bias is not None, False
-            return y.view(*x.shape[:-1], N)
-        wb = weight_bf16(weight)
-        res2 = residual.reshape(-1, weight.shape[0]).contiguous() if residual is not None else None
-        y = Fn.gemm(x2, wb, bias=bias, residual=res2, out_dtype=F32, k=weight.shape[1])
+        else:
+            res2 = residual.reshape(-1, N).contiguous() if residual is not None else None
+            y = Fn.gemm(x2, weight_bf16(weight), bias=bias, residual=res2, out_dtype=F32, k=weight.shape[1])
         ctx.save_for_backward(x2, weight)
-        ctx.x_shape = x.shape
-        ctx.has_bias = bias is not None
-        ctx.has_res = residual is not None
-        ctx.x_needs = x.requires_grad if isinstance(x, torch.Tensor) else False
-        return y.view(*x.shape[:-1], weight.shape[0])
+        return y.view(*x.shape[:-1], N)
 
     @staticmethod
     def backward(ctx, dy):
@@ -253,12 +249,7 @@ class LinearFn(torch.autograd.Function):
             wt = weight_t_bf16(weight)                           # [K, Npad]
             dx = Fn.gemm(dyb, wt, out_dtype=F32, k=N).view(ctx.x_shape)
         if ctx.needs_input_grad[1]:
-            if N % 8 == 0 and K % 8 == 0 and x2.stride(0) % 8 == 0:
-                dw = Fn.gemm_tn(dyb, x2)                         # transposing LDS reads + split-m: no dY^T / X^T passes
-            else:
-                dyt = Fn.operand_t(dy2)                  # [N, Mpad]
-                xt = Fn.operand_t(x2)                    # [K, Mpad]
-                dw = Fn.gemm(dyt, xt, out_dtype=F32, k=dyt.shape[1])  # [N, K]
+            dw = _weight_grad(dy2, dyb, x2, K)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = Fn.colsum(dy2)
         dres = dy if (ctx.has_res and ctx.needs_input_grad[3]) else None
@@ -277,13 +268,9 @@ class LinearCatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, *ws):
-        if Fn.precision() == "fp32" and x.dtype == BF16:
-            x = x.float()
-        xb = x if x.dtype == BF16 else Fn.operand(x.contiguous())
-        K = ws[0].shape[1]
-        x2 = xb.reshape(-1, K)
+        x2 = _input_operand(x)
         wb = weights_cat_bf16(ws)
-        y = Fn.gemm(x2, wb, out_dtype=F32, k=K)
+        y = Fn.gemm(x2, wb, out_dtype=F32, k=ws[0].shape[1])
         ctx.save_for_backward(x2, *ws)
         ctx.x_shape = x.shape
         return y.view(*x.shape[:-1], wb.shape[0])
@@ -300,58 +287,12 @@ class LinearCatFn(torch.autograd.Function):
             dx = Fn.gemm(dyb, weights_cat_t_bf16(ws), out_dtype=F32, k=N).view(ctx.x_shape)
         dws = [None] * len(ws)
         if any(ctx.needs_input_grad[1:]):
-            if N % 8 == 0 and K % 8 == 0 and x2.stride(0) % 8 == 0:
-                dw = Fn.gemm_tn(dyb, x2)
-            else:
-                dyt, xt = Fn.operand_t(dy2), Fn.operand_t(x2)
-                dw = Fn.gemm(dyt, xt, out_dtype=F32, k=dyt.shape[1])
-            dws = list(dw.split([w.shape[0] for w in ws], 0))
+            dws = list(_weight_grad(dy2, dyb, x2, K).split([w.shape[0] for w in ws], 0))
         return (dx, *dws)
 
 
 def linear_cat(x, ws):
     return LinearCatFn.apply(x, *ws)
-
-
-class LinearScaleResidualFn(torch.autograd.Function):
-    """out = (x W^T + b) * lam + res   — a Dinov2 block's `hidden + layer_scale(dense(x))` (modeling_dinov2.py:272-300) as ONE GEMM
-    with the LayerScale and the residual in its epilogue, as the frozen path runs it.  No activation-sized elementwise kernel in
-    the backward either: with G = dY^T X (the transposed GEMM on the UNSCALED dY) and s = colsum(dY),
-        dW = lam[:, None] * G      db = lam * s      dlam = rowsum(W * G) + b * s      dX = dY (lam[:, None] * W)      dres = dY
-    (dlam_n = sum_m dY[m,n] * (x W^T + b)[m,n] regrouped over k: the pre-activation is never stored)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, lam, res):
-        xb = x if x.dtype == BF16 else Fn.operand(x.contiguous())
-        x2 = xb.reshape(-1, xb.shape[-1])
-        N, K = weight.shape
-        res2 = res.reshape(-1, N).contiguous()
-        y = Fn.gemm(x2, weight_bf16(weight), bias=bias.detach(), scale=lam.detach().contiguous(), residual=res2, out_dtype=F32, k=K)
-        ctx.save_for_backward(x2, weight, bias, lam)
-        ctx.x_shape = x.shape
-        return y.view(res.shape)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x2, weight, bias, lam = ctx.saved_tensors
-        N, K = weight.shape
-        dy2 = dy.reshape(-1, N).contiguous()
-        dyb = Fn.operand(dy2)
-        G = Fn.gemm_tn(dyb, x2)                                  # [N, K]
-        s = Fn.colsum(dy2)
-        lam_d, w_d = lam.detach(), weight.detach()
-        dw = lam_d[:, None] * G
-        db = lam_d * s
-        dlam = (w_d * G).sum(dim=1) + bias.detach() * s
-        dx = None
-        if ctx.needs_input_grad[0]:
-            wl_t = Fn.operand_t((lam_d[:, None] * w_d).contiguous())         # [K, N] bf16: dX = dY (lam * W)
-            dx = Fn.gemm(dyb, wl_t, out_dtype=F32, k=N).view(ctx.x_shape)
-        return dx, dw, db, dlam, dy
-
-
-def linear_scale_residual(x, weight, bias, lam, res):
-    return LinearScaleResidualFn.apply(x, weight, bias, lam, res)
 
 
 class InProjFn(torch.autograd.Function):
@@ -363,8 +304,7 @@ class InProjFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xq, xkv, weight, bias, d):
         K = weight.shape[1]
-        q2 = Fn.operand(xq.contiguous()).reshape(-1, K)
-        kv2 = Fn.operand(xkv.contiguous()).reshape(-1, K)
+        q2, kv2 = _input_operand(xq), _input_operand(xkv)
         wb = weight_bf16(weight)
         Q = Fn.gemm(q2, wb[:d], bias=bias[:d], out_dtype=F32, k=K)
         KV = Fn.gemm(kv2, wb[d:], bias=bias[d:], out_dtype=F32, k=K)
@@ -458,24 +398,39 @@ def gelu_dropout(x, p=0.0, seed=0, sid=0, lowp=False):
     return GeluDropoutFn.apply(x, float(p), int(seed), int(sid))
 
 
+def _dropout_launch(x, residual, cfg, what):
+    """(residual +) dropout(x) under the mask of cfg = (p, seed, sid); the backward is the same launch on the gradient."""
+    xc = x.contiguous()
+    rc = residual.contiguous() if residual is not None else None
+    out = torch.empty_like(xc)
+    check(lib().medp_dropout_add(ptr(xc), ptr(rc), ptr(out), xc.numel(), *cfg, stream()), what)
+    return out
+
+
 class DropoutAddFn(torch.autograd.Function):
     """out = residual + dropout(y)."""
 
     @staticmethod
     def forward(ctx, y, residual, p, seed, sid):
-        yc, rc = y.contiguous(), residual.contiguous()
-        out = torch.empty_like(yc)
-        check(lib().medp_dropout_add(ptr(yc), ptr(rc), ptr(out), yc.numel(), p, seed, sid, stream()), "dropout_add")
         ctx.cfg = (p, seed, sid)
-        return out
+        return _dropout_launch(y, residual, ctx.cfg, "dropout_add")
 
     @staticmethod
     def backward(ctx, dout):
-        p, seed, sid = ctx.cfg
-        dc = dout.contiguous()
-        dy = torch.empty_like(dc)
-        check(lib().medp_dropout_add(ptr(dc), None, ptr(dy), dc.numel(), p, seed, sid, stream()), "dropout_add(bwd)")
-        return dy, dout, None, None, None
+        return _dropout_launch(dout, None, ctx.cfg, "dropout_add(bwd)"), dout, None, None, None
+
+
+class DropoutFn(torch.autograd.Function):
+    """out = dropout(x)."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, sid):
+        ctx.cfg = (p, seed, sid)
+        return _dropout_launch(x, None, ctx.cfg, "dropout")
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _dropout_launch(dout, None, ctx.cfg, "dropout(bwd)"), None, None, None
 
 
 def dropout_add(y, residual, p, seed, sid):
@@ -710,24 +665,6 @@ def masked_bce_global(logits, y, mask):
     yc, mc = (t.detach().contiguous().to(F32) for t in (y, mask))
     return _ScalarLossFn.apply(logits, lambda x, out, g: check(
         lib().medp_masked_bce_global(ptr(x), ptr(yc), ptr(mc), ptr(out), ptr(g), x.numel(), stream()), "masked_bce_global"))
-
-
-class DropoutFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, p, seed, sid):
-        xc = x.contiguous()
-        out = torch.empty_like(xc)
-        check(lib().medp_dropout_add(ptr(xc), None, ptr(out), xc.numel(), p, seed, sid, stream()), "dropout")
-        ctx.cfg = (p, seed, sid)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        p, seed, sid = ctx.cfg
-        dc = dout.contiguous()
-        dx = torch.empty_like(dc)
-        check(lib().medp_dropout_add(ptr(dc), None, ptr(dx), dc.numel(), p, seed, sid, stream()), "dropout(bwd)")
-        return dx, None, None, None
 
 
 class _AddScaledFn(torch.autograd.Function):

@@ -8,6 +8,7 @@ The backbone is frozen in the reference's live configuration (trainer.py:287-289
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
 from dataclasses import dataclass
 
 import torch
@@ -69,6 +70,28 @@ def dinov2_param_shapes(cfg: Dinov2Cfg) -> dict:
     return sh
 
 
+_BLOCK_KEYS = {"ln1_w": "norm1.weight", "ln1_b": "norm1.bias",
+               "wq": "attention.attention.query.weight", "wk": "attention.attention.key.weight", "wv": "attention.attention.value.weight",
+               "bq": "attention.attention.query.bias", "bk": "attention.attention.key.bias", "bv": "attention.attention.value.bias",
+               "wo": "attention.output.dense.weight", "bo": "attention.output.dense.bias", "ls1": "layer_scale1.lambda1",
+               "ln2_w": "norm2.weight", "ln2_b": "norm2.bias", "w1": "mlp.fc1.weight", "b1": "mlp.fc1.bias",
+               "w2": "mlp.fc2.weight", "b2": "mlp.fc2.bias", "ls2": "layer_scale2.lambda1"}
+BlockParams = namedtuple("BlockParams", tuple(_BLOCK_KEYS))
+
+
+def block_params(sd, l: int) -> BlockParams:
+    """The tensors of encoder block `l` out of a name -> tensor mapping, exactly as they are in it (no detach, no cast)."""
+    return BlockParams(*(sd[f"encoder.layer.{l}.{k}"] for k in _BLOCK_KEYS.values()))
+
+
+def padded_patch_weight(weight: torch.Tensor) -> torch.Tensor:
+    """The patch convolution's weight [D, C, p, p] as the GEMM weight [D, kpad] fp32, kpad = C p^2 rounded up to 8, pad columns zero."""
+    D, K = weight.shape[0], weight[0].numel()
+    wpad = torch.zeros((D, (K + 7) // 8 * 8), dtype=torch.float32, device=weight.device)
+    wpad[:, :K] = weight.detach().reshape(D, K)
+    return wpad
+
+
 class Dinov2Backbone(nn.Module):
     """Parameter holder with Dinov2Model's key layout; `forward` is the HIP whole-module call."""
 
@@ -103,7 +126,6 @@ class Dinov2Backbone(nn.Module):
             return self._prep
         c = self.cfg
         D = c.hidden_size
-        dev = sd["layernorm.weight"].device
         keep = []          # keep every device buffer alive as long as the structs point at them
 
         def f32(t):
@@ -116,27 +138,22 @@ class Dinov2Backbone(nn.Module):
             keep.append(t)
             return t
 
-        K = c.num_channels * c.patch_size ** 2
-        kpad = (K + 7) // 8 * 8
-        pw = torch.zeros((D, kpad), dtype=torch.float32, device=dev)
-        pw[:, :K] = sd["embeddings.patch_embeddings.projection.weight"].detach().reshape(D, K)
+        pw = padded_patch_weight(sd["embeddings.patch_embeddings.projection.weight"])
         layers = (MedpVitLayer * c.num_hidden_layers)()
         for l in range(c.num_hidden_layers):
-            p = f"encoder.layer.{l}."
-            L = layers[l]
-            qkv_w = torch.cat([sd[p + f"attention.attention.{n}.weight"].detach() for n in ("query", "key", "value")], 0)
-            qkv_b = torch.cat([sd[p + f"attention.attention.{n}.bias"].detach() for n in ("query", "key", "value")], 0)
-            L.ln1_w, L.ln1_b = ptr(f32(sd[p + "norm1.weight"])), ptr(f32(sd[p + "norm1.bias"]))
+            L, blk = layers[l], block_params(sd, l)
+            qkv_w = torch.cat([blk.wq.detach(), blk.wk.detach(), blk.wv.detach()], 0)
+            qkv_b = torch.cat([blk.bq.detach(), blk.bk.detach(), blk.bv.detach()], 0)
+            L.ln1_w, L.ln1_b = ptr(f32(blk.ln1_w)), ptr(f32(blk.ln1_b))
             L.qkv_w, L.qkv_b = ptr(bf(qkv_w)), ptr(f32(qkv_b))
-            L.proj_w, L.proj_b = ptr(bf(sd[p + "attention.output.dense.weight"])), ptr(f32(sd[p + "attention.output.dense.bias"]))
-            L.ls1 = ptr(f32(sd[p + "layer_scale1.lambda1"]))
-            L.ln2_w, L.ln2_b = ptr(f32(sd[p + "norm2.weight"])), ptr(f32(sd[p + "norm2.bias"]))
-            L.fc1_w, L.fc1_b = ptr(bf(sd[p + "mlp.fc1.weight"])), ptr(f32(sd[p + "mlp.fc1.bias"]))
-            L.fc2_w, L.fc2_b = ptr(bf(sd[p + "mlp.fc2.weight"])), ptr(f32(sd[p + "mlp.fc2.bias"]))
-            L.ls2 = ptr(f32(sd[p + "layer_scale2.lambda1"]))
+            L.proj_w, L.proj_b = ptr(bf(blk.wo)), ptr(f32(blk.bo))
+            L.ls1 = ptr(f32(blk.ls1))
+            L.ln2_w, L.ln2_b = ptr(f32(blk.ln2_w)), ptr(f32(blk.ln2_b))
+            L.fc1_w, L.fc1_b = ptr(bf(blk.w1)), ptr(f32(blk.b1))
+            L.fc2_w, L.fc2_b = ptr(bf(blk.w2)), ptr(f32(blk.b2))
+            L.ls2 = ptr(f32(blk.ls2))
             # LayerNorm fold operands (include/medp_hip.h): W g in bf16, the row sums of THAT rounded matrix, b + W beta
-            for name, W, b, g, beta in (("qkv", qkv_w, qkv_b, sd[p + "norm1.weight"], sd[p + "norm1.bias"]),
-                                        ("fc1", sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"], sd[p + "norm2.weight"], sd[p + "norm2.bias"])):
+            for name, W, b, g, beta in (("qkv", qkv_w, qkv_b, blk.ln1_w, blk.ln1_b), ("fc1", blk.w1, blk.b1, blk.ln2_w, blk.ln2_b)):
                 W32 = W.detach().to(torch.float32)
                 wg = bf(W32 * g.detach().to(torch.float32)[None, :])
                 setattr(L, name + "_wg", ptr(wg))
@@ -144,7 +161,7 @@ class Dinov2Backbone(nn.Module):
                 setattr(L, name + "_b2", ptr(f32(b.detach().to(torch.float32) + W32 @ beta.detach().to(torch.float32))))
         w = MedpVitWeights()
         w.hidden, w.n_layers, w.n_heads, w.mlp_hidden = D, c.num_hidden_layers, c.num_attention_heads, D * c.mlp_ratio
-        w.patch, w.pos_side, w.patch_kpad, w.ln_eps = c.patch_size, c.image_size // c.patch_size, kpad, c.layer_norm_eps
+        w.patch, w.pos_side, w.patch_kpad, w.ln_eps = c.patch_size, c.image_size // c.patch_size, pw.shape[1], c.layer_norm_eps
         w.patch_w = ptr(bf(pw))
         w.patch_b = ptr(f32(sd["embeddings.patch_embeddings.projection.bias"]))
         w.cls = ptr(f32(sd["embeddings.cls_token"].reshape(-1)))

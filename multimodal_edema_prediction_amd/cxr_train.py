@@ -9,7 +9,7 @@ here from autograd nodes over the same HIP kernels:
   attention (forward with logsumexp / MFMA flash backward of attention_dh64_bwd.hip) and the fc1 pre-activation all hand bf16
   to the next kernel, LayerScale + residual ride in the epilogue of the projection / fc2 GEMM, and their gradients (dW, db,
   dlambda) come from the unscaled transposed GEMM, so no activation-sized elementwise or cast kernel runs between the stages;
-  only the residual stream is fp32.  (`AttnDh64Fn` is the stand-alone attention node of the first, op-by-op composition.)
+  only the residual stream is fp32.
 
 Parity: tests/test_gpu_unfrozen_cxr.py against the oracle's autograd.
 """
@@ -20,9 +20,9 @@ import torch
 from . import autograd_ops as A
 from . import functional as Fn
 from .abi import check, lib, ptr, stream
+from .cxr import block_params, padded_patch_weight
 
 BF16, F32 = torch.bfloat16, torch.float32
-_SMALL_BWD = __import__("os").environ.get("MEDP_ATTN_BWD", "") == "small"
 
 
 class PatchEmbedFn(torch.autograd.Function):
@@ -37,9 +37,7 @@ class PatchEmbedFn(torch.autograd.Function):
         cols = torch.empty((B * gh * gw, kpad), dtype=BF16, device=pixels.device)
         px = pixels.detach().to(F32).contiguous()
         check(lib().medp_im2col_patch(ptr(px), ptr(cols), B, C, H, W, patch, kpad, stream()), "im2col_patch")
-        wpad = torch.zeros((D, kpad), dtype=F32, device=pixels.device)
-        wpad[:, :K] = weight.detach().reshape(D, K)
-        y = Fn.gemm(cols, Fn.to_bf16(wpad), bias=bias.detach(), out_dtype=F32, k=kpad)
+        y = Fn.gemm(cols, Fn.to_bf16(padded_patch_weight(weight)), bias=bias.detach(), out_dtype=F32, k=kpad)
         ctx.save_for_backward(cols)
         ctx.wshape, ctx.K = weight.shape, K
         return y.view(B, gh * gw, D)
@@ -76,40 +74,19 @@ class PosBicubicFn(torch.autograd.Function):
         return dpos.view(shape), None, None, None
 
 
-class AttnDh64Fn(torch.autograd.Function):
-    """qkv fp32 [B*S, 3*H*64] (q | k | v column blocks) -> o fp32 [B*S, H*64].  Forward and backward are the head-dim-64 MFMA
-    flash kernels (attention_dh64.hip / attention_dh64_bwd.hip); `MEDP_ATTN_BWD=small` selects the fp32 small-attention
-    backward instead (the first, slow implementation — kept as a cross-check)."""
-
-    @staticmethod
-    def forward(ctx, qkv, B, S, H):
-        qkv16 = Fn.to_bf16(qkv.contiguous())
-        o, lse = Fn.attn_dh64_lse(qkv16, B, S, H, 0.125)
-        ctx.save_for_backward(qkv, qkv16, o, lse)
-        ctx.dims = (B, S, H)
-        return o.float()
-
-    @staticmethod
-    def backward(ctx, do):
-        qkv, qkv16, o, lse = ctx.saved_tensors
-        B, S, H = ctx.dims
-        D = H * 64
-        if _SMALL_BWD:
-            q3 = qkv.view(B, S, 3 * D)
-            q, k, v = q3[..., :D], q3[..., D:2 * D], q3[..., 2 * D:]
-            dq, dk, dv = Fn.attn_small_bwd(do.contiguous().view(B, S, D), q, k, v, B, S, S, H, 64, 0.125,
-                                           q_batch_stride=S * 3 * D, kv_batch_stride=S * 3 * D)
-            return torch.cat([dq, dk, dv], dim=-1).view(B * S, 3 * D), None, None, None
-        return Fn.attn_dh64_bwd(do, qkv16, o, lse, B, S, H, 0.125), None, None, None
-
-
-def _ls_linear_backward(dy2, dyb, x16, weight, bias, lam, need_dx=True):
-    """Gradients of out = (x W^T + b) * lam + res given dY (fp32) and its bf16 copy: (dX fp32 | None, dW, db, dlam) — no
-    activation-sized elementwise kernel (see autograd_ops.LinearScaleResidualFn)."""
+def ls_linear_backward(dy2, dyb, x16, weight, bias, lam, dx_dtype=F32):
+    """Gradients of out = (x W^T + b) * lam + res — a Dinov2 block's `hidden + layer_scale(dense(x))` (modeling_dinov2.py:272-300),
+    run as ONE GEMM with LayerScale and residual in its epilogue — given dY (fp32 [M, N]), its bf16 copy and the bf16 input x16 [M, K]:
+    (dX in `dx_dtype`, fp32 or bf16, or None for `dx_dtype=None`; dW; db; dlam); dres is dY itself.  No activation-sized elementwise
+    kernel: with G = dY^T X (the transposed GEMM on the UNSCALED dY) and s = colsum(dY),
+        dW = lam[:, None] * G      db = lam * s      dlam = rowsum(W * G) + b * s      dX = dY (lam[:, None] * W)
+    (dlam_n = sum_m dY[m,n] * (x W^T + b)[m,n] regrouped over k: the pre-activation is never stored)."""
     G = Fn.gemm_tn(dyb, x16)
     s = Fn.colsum(dy2)
     lam_d, w_d = lam.detach(), weight.detach()
-    dx = Fn.gemm(dyb, Fn.transpose_to_bf16((lam_d[:, None] * w_d).contiguous()), out_dtype=F32, k=weight.shape[0]) if need_dx else None
+    dx = None
+    if dx_dtype is not None:
+        dx = Fn.gemm(dyb, Fn.transpose_to_bf16((lam_d[:, None] * w_d).contiguous()), out_dtype=dx_dtype, k=weight.shape[0])
     return dx, lam_d[:, None] * G, lam_d * s, (w_d * G).sum(dim=1) + bias.detach() * s
 
 
@@ -139,7 +116,7 @@ class AttnHalfFn(torch.autograd.Function):
         D = H * 64
         dy2 = dy.contiguous()
         dyb = Fn.to_bf16(dy2)
-        do, dwo, dbo, dlam = _ls_linear_backward(dy2, dyb, o16, wo, bo, lam)
+        do, dwo, dbo, dlam = ls_linear_backward(dy2, dyb, o16, wo, bo, lam, F32)
         dqkv = Fn.attn_dh64_bwd(do, qkv16, o16, lse, B, S, H, 0.125)                  # fp32 [M, 3D]
         dqkvb = Fn.to_bf16(dqkv)
         dwqkv = Fn.gemm_tn(dqkvb, h16)
@@ -172,11 +149,7 @@ class MlpHalfFn(torch.autograd.Function):
         x, mean, rstd, h16, pre16, f16, ln_w, w1, w2, b2, lam = ctx.saved_tensors
         dy2 = dy.contiguous()
         dyb = Fn.to_bf16(dy2)
-        G2 = Fn.gemm_tn(dyb, f16)
-        s = Fn.colsum(dy2)
-        lam_d, w2_d = lam.detach(), w2.detach()
-        dw2, db2, dlam = lam_d[:, None] * G2, lam_d * s, (w2_d * G2).sum(dim=1) + b2.detach() * s
-        df16 = Fn.gemm(dyb, Fn.transpose_to_bf16((lam_d[:, None] * w2_d).contiguous()), out_dtype=BF16, k=w2.shape[0])
+        df16, dw2, db2, dlam = ls_linear_backward(dy2, dyb, f16, w2, b2, lam, BF16)
         dpre16 = torch.empty_like(df16)
         check(lib().medp_gelu_bf16_bwd(ptr(df16), ptr(pre16), ptr(dpre16), df16.numel(), stream()), "gelu_bf16_bwd")
         dw1 = Fn.gemm_tn(dpre16, h16)
@@ -185,6 +158,18 @@ class MlpHalfFn(torch.autograd.Function):
         dh = Fn.gemm(dpre16, A.weight_t_bf16(w1), out_dtype=F32, k=w1.shape[0])
         dx_ln, dlnw, dlnb = Fn.layernorm_bwd(dh, x, ln_w.detach(), mean, rstd)
         return dy2 + dx_ln, dlnw, dlnb, dw1, db1, dw2, db2, dlam, None
+
+
+def _token_stream(sd, patch, c, gh, gw):
+    """cls | patch tokens [B, gh*gw, D], plus the position embeddings -> [B, 1 + gh*gw, D]."""
+    B, _, D = patch.shape
+    cls = sd["embeddings.cls_token"].reshape(1, 1, D).expand(B, 1, D)
+    pos = sd["embeddings.position_embeddings"].reshape(1, -1, D)
+    side = c.image_size // c.patch_size
+    if (gh, gw) != (side, side):
+        # modeling_dinov2.py:57-95: bicubic resize of the stored patch grid (align_corners=False)
+        pos = PosBicubicFn.apply(sd["embeddings.position_embeddings"], side, gh, gw)
+    return torch.cat([cls, patch], dim=1) + pos
 
 
 def forward_training(backbone, pixel_values: torch.Tensor) -> torch.Tensor:
@@ -198,24 +183,13 @@ def forward_training(backbone, pixel_values: torch.Tensor) -> torch.Tensor:
     gh, gw = Hh // c.patch_size, Ww // c.patch_size
     patch = PatchEmbedFn.apply(pixel_values, sd["embeddings.patch_embeddings.projection.weight"],
                                sd["embeddings.patch_embeddings.projection.bias"], c.patch_size)
-    cls = sd["embeddings.cls_token"].reshape(1, 1, D).expand(B, 1, D)
-    pos = sd["embeddings.position_embeddings"].reshape(1, -1, D)
-    side = c.image_size // c.patch_size
-    if not (gh == side and gw == side):
-        # modeling_dinov2.py:57-95: bicubic resize of the stored patch grid (align_corners=False)
-        pos = PosBicubicFn.apply(sd["embeddings.position_embeddings"], side, gh, gw)
-    x = torch.cat([cls, patch], dim=1) + pos
+    x = _token_stream(sd, patch, c, gh, gw)
     S = x.shape[1]
     x = x.reshape(B * S, D)
     for l in range(c.num_hidden_layers):
-        p = f"encoder.layer.{l}."
-        a = p + "attention.attention."
-        x = AttnHalfFn.apply(x, sd[p + "norm1.weight"], sd[p + "norm1.bias"], sd[a + "query.weight"], sd[a + "key.weight"],
-                             sd[a + "value.weight"], sd[a + "query.bias"], sd[a + "key.bias"], sd[a + "value.bias"],
-                             sd[p + "attention.output.dense.weight"], sd[p + "attention.output.dense.bias"],
-                             sd[p + "layer_scale1.lambda1"], c.layer_norm_eps, B, S, H)
-        x = MlpHalfFn.apply(x, sd[p + "norm2.weight"], sd[p + "norm2.bias"], sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"],
-                            sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"], sd[p + "layer_scale2.lambda1"], c.layer_norm_eps)
+        b = block_params(sd, l)
+        x = AttnHalfFn.apply(x, b.ln1_w, b.ln1_b, b.wq, b.wk, b.wv, b.bq, b.bk, b.bv, b.wo, b.bo, b.ls1, c.layer_norm_eps, B, S, H)
+        x = MlpHalfFn.apply(x, b.ln2_w, b.ln2_b, b.w1, b.b1, b.w2, b.b2, b.ls2, c.layer_norm_eps)
     x = A.layer_norm(x, sd["layernorm.weight"], sd["layernorm.bias"], c.layer_norm_eps)
     return x.view(B, S, D)
 
@@ -239,27 +213,20 @@ def forward_fp32(backbone, pixel_values: torch.Tensor) -> torch.Tensor:
     cols = px[:, :, :gh * P, :gw * P].unfold(2, P, P).unfold(3, P, P).permute(0, 2, 3, 1, 4, 5).reshape(B * gh * gw, C * P * P).contiguous()
     patch = Fn.gemm(cols, sd["embeddings.patch_embeddings.projection.weight"].reshape(D, C * P * P).contiguous(),
                     bias=sd["embeddings.patch_embeddings.projection.bias"]).view(B, gh * gw, D)
-    side = c.image_size // P
-    pos = sd["embeddings.position_embeddings"].reshape(1, -1, D)
-    if not (gh == side and gw == side):
-        pos = PosBicubicFn.apply(sd["embeddings.position_embeddings"], side, gh, gw)
-    x = (torch.cat([sd["embeddings.cls_token"].reshape(1, 1, D).expand(B, 1, D), patch], dim=1) + pos).contiguous()
+    x = _token_stream(sd, patch, c, gh, gw).contiguous()
     S = x.shape[1]
     x = x.view(B * S, D)
     for l in range(c.num_hidden_layers):
-        p = f"encoder.layer.{l}."
-        a = p + "attention.attention."
-        h = Fn.layernorm(x, sd[p + "norm1.weight"], sd[p + "norm1.bias"], c.layer_norm_eps, out_dtype=F32)
-        wqkv = torch.cat([sd[a + "query.weight"], sd[a + "key.weight"], sd[a + "value.weight"]], 0).contiguous()
-        bqkv = torch.cat([sd[a + "query.bias"], sd[a + "key.bias"], sd[a + "value.bias"]], 0).contiguous()
+        b = block_params(sd, l)
+        h = Fn.layernorm(x, b.ln1_w, b.ln1_b, c.layer_norm_eps, out_dtype=F32)
+        wqkv = torch.cat([b.wq, b.wk, b.wv], 0).contiguous()
+        bqkv = torch.cat([b.bq, b.bk, b.bv], 0).contiguous()
         qkv = Fn.gemm(h, wqkv, bias=bqkv).view(B, S, 3 * D)
         o = Fn.attn_small_fwd(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], B, S, S, H, 64, 0.125, q_batch_stride=S * 3 * D,
                               kv_batch_stride=S * 3 * D)
-        x = Fn.gemm(o.reshape(B * S, D), sd[p + "attention.output.dense.weight"].contiguous(), bias=sd[p + "attention.output.dense.bias"],
-                    scale=sd[p + "layer_scale1.lambda1"].contiguous(), residual=x)
-        h = Fn.layernorm(x, sd[p + "norm2.weight"], sd[p + "norm2.bias"], c.layer_norm_eps, out_dtype=F32)
-        f = Fn.gemm(h, sd[p + "mlp.fc1.weight"].contiguous(), bias=sd[p + "mlp.fc1.bias"], act=1)
-        x = Fn.gemm(f, sd[p + "mlp.fc2.weight"].contiguous(), bias=sd[p + "mlp.fc2.bias"], scale=sd[p + "layer_scale2.lambda1"].contiguous(),
-                    residual=x)
+        x = Fn.gemm(o.reshape(B * S, D), b.wo.contiguous(), bias=b.bo, scale=b.ls1.contiguous(), residual=x)
+        h = Fn.layernorm(x, b.ln2_w, b.ln2_b, c.layer_norm_eps, out_dtype=F32)
+        f = Fn.gemm(h, b.w1.contiguous(), bias=b.b1, act=1)
+        x = Fn.gemm(f, b.w2.contiguous(), bias=b.b2, scale=b.ls2.contiguous(), residual=x)
     x = Fn.layernorm(x, sd["layernorm.weight"], sd["layernorm.bias"], c.layer_norm_eps, out_dtype=F32)
     return x.view(B, S, D)

@@ -154,7 +154,7 @@ class _CapturedStep:
         # writes a frozen parameter or buffer and then calls the module eagerly: keep what the capture saw alive, and refuse to
         # replay over changed weights (`_replay`) instead of training on stale ones.
         self._prep_refs = [(m, m._prep) for root in self._stateful_modules() for m in root.modules() if getattr(m, "_prep", None) is not None]
-        self._cache_refs = [v for slot in _A._W_CACHE.values() for v in slot.values()]
+        self._cache_refs = _A.live_operands()
         # ... and into the modules' workspaces and pointer / length tables: an eager call with a larger batch or image
         # REPLACES a workspace (cxr.Dinov2Backbone._ws[slot], duett.Model._ws), the 16-entry table cache of feats_to_input evicts.
         # Holding what the capture saw keeps that memory allocated, so a replay after such a call still reads and writes live buffers

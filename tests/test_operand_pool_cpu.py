@@ -1,6 +1,8 @@
 """Host logic of autograd_ops.WeightOperandPool (the job table behind `medp_weight_operands_multi`): which weights get a plain / a transposed
-bf16 operand, where q | k | v land inside their stacked operand, how many 64 x 64 tiles each job is cut into.  No kernel runs here."""
+bf16 operand, where q | k | v land inside their stacked operand, how many 64 x 64 tiles each job is cut into; and of the operand cache it
+files them in (`_fetch` / `_store` behind `_cached` / `_cached_group`): owner, view, versions, partners.  No kernel runs here."""
 import ctypes
+import gc
 
 import torch
 
@@ -61,3 +63,57 @@ def test_group_cache_is_keyed_on_identity_and_versions():
     assert v2 is not v1 and len(made) == 2 and torch.equal(v2[4:], b.detach())
     c = torch.nn.Parameter(torch.randn(4, 8))
     assert A._cached_group((a, c), "k", make) is not v2 and len(made) == 3                       # another partner under the same first weight
+
+
+def test_single_entry_is_served_until_the_weight_changes():
+    w = torch.nn.Parameter(torch.randn(8, 8))
+    made = []
+    make = lambda t: made.append(1) or t.clone()
+    stored = torch.zeros(8, 8)
+    A._store((w,), "k", stored)
+    assert A._cached(w, "k", make) is stored and not made                                        # found: `make` is not called
+    torch.autograd.graph.increment_version(w)
+    v = A._cached(w, "k", make)
+    assert v is not stored and len(made) == 1 and A._cached(w, "k", make) is v and len(made) == 1
+
+
+def test_a_view_and_its_parameter_have_separate_entries_under_one_owner():
+    w = torch.nn.Parameter(torch.randn(8, 8))
+    made = []
+    make = lambda t: made.append(tuple(t.shape)) or t.clone()
+    whole = A._store((w,), "k", torch.zeros(8, 8))
+    top = A._cached(w[:4], "k", make)                                                            # the whole weight's entry does not serve its rows
+    assert made == [(4, 8)] and top.shape == (4, 8)
+    assert A._cached(w[:4], "k", make) is top and A._cached(w, "k", make) is whole and len(made) == 1
+    A._store((w[4:],), "k", torch.ones(4, 8))                                                    # another view: neither of the two is touched
+    assert A._cached(w[:4], "k", make) is top and A._cached(w, "k", make) is whole and len(made) == 1
+    mine = lambda: sum(1 for v in A.live_operands() if v is top or v is whole)
+    assert mine() == 2
+    del w                                                                                        # one owner: both leave with the parameter
+    gc.collect()
+    assert mine() == 0
+
+
+def test_stored_group_entry_is_keyed_on_every_member():
+    P = lambda: torch.nn.Parameter(torch.randn(4, 8))
+    a, b, c = P(), P(), P()
+    made = []
+    make = lambda ts: made.append(1) or torch.cat(ts, 0)
+    stored = torch.zeros(12, 8)
+    A._store((a, b, c), "k", stored)
+    assert A._cached_group((a, b, c), "k", make) is stored and not made
+    torch.autograd.graph.increment_version(b)                                                    # the middle one changed: rebuilt
+    v = A._cached_group((a, b, c), "k", make)
+    assert v is not stored and len(made) == 1 and A._cached_group((a, b, c), "k", make) is v
+    d = P()                                                                                      # equal shape, another object
+    v2 = A._cached_group((a, b, d), "k", make)
+    assert v2 is not v and len(made) == 2 and torch.equal(v2[8:], d.detach())
+
+
+def test_live_operands_forget_a_deleted_parameter():
+    w =torch.nn.Parameter(torch.randn(4, 8))
+    val = A._cached(w, "k", lambda t: t.clone())
+    assert any(v is val for v in A.live_operands())
+    del w
+    gc.collect()
+    assert not any(v is val for v in A.live_operands())
