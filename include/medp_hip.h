@@ -180,6 +180,7 @@ int medp_scalenorm_bwd_add(const float* dy, int lddy, const float* x, int ldx, c
                            int ldadd, float* dx, int lddx, float* dg, float* workspace_rows, int rows, int D, void* stream);
 
 /* ---- layout / pointwise ------------------------------------------------------------------------------ */
+/* y[r][c] = (bf16) x[r][c]: cols, ldx, ldy multiples of 4; ldy >= cols unless rows == 1 (ldx may be smaller than cols: a broadcast row) */
 int medp_cast_f32_bf16(const float* x, int ldx, void* y, int ldy, int rows, int cols, void* stream);
 int medp_transpose_to_bf16(const void* x, int x_is_bf16, int ldx, void* y, int ldy, int rows, int cols, void* stream);
 /* The bf16 GEMM operands of MANY fp32 weight matrices in one launch (the per-step casts of a training step's trainable weights: each

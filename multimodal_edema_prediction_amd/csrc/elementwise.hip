@@ -246,6 +246,7 @@ __global__ __launch_bounds__(256) void pos_bicubic_bwd_kernel(const float* __res
 extern "C" int medp_cast_f32_bf16(const float* x, int ldx, void* y, int ldy, int rows, int cols, void* stream) {
     MEDP_CHECK_ARG(x && y && rows > 0 && cols > 0, "cast: bad argument");
     MEDP_CHECK_ARG(cols % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, "cast: cols, ldx, ldy must be multiples of 4");
+    MEDP_CHECK_ARG(rows == 1 || ldy >= cols, "cast: ldy %d < cols %d (the rows of y would overlap and the last one end past rows * ldy)", ldy, cols);
     cast_f32_bf16_kernel<<<grid_for((size_t)rows * cols / 4), 256, 0, (hipStream_t)stream>>>(x, ldx, (bf16_t*)y, ldy, rows, cols);
     MEDP_LAUNCH_CHECK("medp_cast_f32_bf16");
     return 0;
