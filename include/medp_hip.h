@@ -607,6 +607,101 @@ int medp_head_train_epoch(const MedpHeadProblem* table_host, const MedpHeadProbl
 int medp_head_scores(const float* X, long long ldx, int N, int col0, int F, int L, int label_width, const float* W, const float* b,
                      const int* rows, int n, float* logits, double* probs, void* stream);
 
+/* ---- Probe heads with a hidden stage (csrc/pool_head_probe.hip) ---------------------------------------------------------------
+ * The two heads of the linear-head probes that are not a plain linear map.  fp32 in storage, fp64 accumulators, no floating-point
+ * atomics, no wait between workgroups, every reduction in a fixed order: two calls from the same state are bit-identical.
+ *
+ * Attention-pooled head (LinearHead(use_attn_pool=True)): over X [N, T, d] contiguous,
+ *     s_t = x_t . q / sqrt(d),  w = softmax_t(s),  pooled = sum_t w_t x_t,  z = (pooled o dropout) W^T + b,
+ *   the masked BCE of medp_head_train_epoch (vc = the known labels of the whole minibatch; vc = 0: zero gradients, AdamW still
+ *   steps), torch's AdamW with weight decay on q [d], W [L, d] and b [L].
+ * medp_pool_head_train_epoch: the S = pb->S steps of one epoch, TWO launches per step, all enqueued on `stream` by this one call
+ *   (no host work between steps that waits for the device, no copy, no synchronisation).  Step s (step number k = step0 + s + 1):
+ *     row kernel     grid bs, workgroup r takes row perm[s bs + r]: scores, softmax, pooled, the dropout factor of element r d + j
+ *                    from the counter hash of (seed + k * 0x9E3779B9, stream_id, r d + j), logits, vc (every workgroup sums the
+ *                    bs L mask values itself, in the same order), g = (sigmoid(z) - y) M / vc, the row's loss part and its backward
+ *                    down to dq_row; writes pooled o dropout [d], g [L padded], the loss part and dq_row [d] into `ws`;
+ *     column kernel  thread per column j: dW[:, j] and dq[j] summed over the rows IN ORDER in fp64, AdamW on W[:, j] and q[j];
+ *                    block 0 also steps b and adds the step's (loss vc, vc) to loss_out [2] (set, not added, at s = 0).
+ *   The row's T d tokens stay in LDS for the whole row kernel when medp_pool_head_rows_onchip(T, d) = 1 (16 T + 4 T d bytes within
+ *   144 KiB), and are re-read from global memory / L2 otherwise.  The step number is the host scalar step0: the caller adds S
+ *   after every call; there is no device counter.  `ws`: medp_pool_head_ws_bytes(d, L, bs) bytes, 16-byte aligned, contents
+ *   undefined between calls.  perm_host [S bs] is checked before anything is launched (every entry in [0, N)); pb->perm is the
+ *   same array in device memory and is what the kernels read.  rc < 0, nothing launched: a null pointer, T outside [1, 1024],
+ *   d outside [1, MEDP_HEAD_MAX_F], L outside [1, MEDP_HEAD_MAX_L], bs outside [1, MEDP_HEAD_MAX_BS], S < 1 or S bs > N, ldy < L,
+ *   dropout_p outside [0, 1), step0 < 0, bad AdamW scalars, a permutation entry outside [0, N); a null pb->perm is reported
+ *   last, so every other check can be driven without a device.
+ * medp_pool_head_scores: the row kernel's forward without dropout for the rows `rows` [n] (int32; null: rows 0 .. n-1):
+ *   logits [n, L] fp32 and probs [L, n] fp64 = the fp32 value 1 / (1 + exp(-logit)) widened, as medp_head_scores writes them.
+ *   A row outside [0, N) is not dereferenced: NaN.
+ *
+ * MLP fusion head (LogitFusionHead("mlp")): z = W2 (dropout o gelu(W1 x + b1)) + b2 over the K columns X[r, col0 .. col0 + K), GELU
+ *   exact (erf), W1 [H, K], W2 [L, H].
+ * medp_mlp_head_train_epoch: P problems, one 512-thread workgroup each, ALL steps of the epoch in one launch, as
+ *   medp_head_train_epoch: the four parameter tensors and their Adam moments live in LDS for the epoch, as do the minibatch's
+ *   pre-activations and masked hidden activations.  The dropout factor of hidden element r H + k of step number k' = t + 1 comes
+ *   from (seed + k' * 0x9E3779B9, stream_id, r H + k); t[0] (device) is advanced by S.  Every gradient sum takes the rows in
+ *   order, in fp64.  medp_mlp_head_supported(K, L, H, bs) = 1 when 8 bs H + 4 bs Lpad + 12 (H K + H + L H + L) bytes fit 144 KiB
+ *   (Lpad = 2, 8 or 16).  perm_host of every problem is checked before the launch, as above; rc < 0, nothing launched: a null
+ *   pointer, P outside [1, 65535], K outside [1, MEDP_MLP_HEAD_MAX_K], H outside [1, MEDP_MLP_HEAD_MAX_H], L, bs, S, ldx, ldy,
+ *   dropout_p, AdamW scalars as above, an unsupported shape, a permutation entry outside [0, N); a null table_dev last.
+ * medp_mlp_head_scores: logits [n, L] fp32 and probs [L, n] fp64 of the rows `rows` (null: rows 0 .. n-1), no dropout. */
+#define MEDP_POOL_HEAD_MAX_T 1024
+#define MEDP_MLP_HEAD_MAX_K 64
+#define MEDP_MLP_HEAD_MAX_H 1024
+typedef struct {
+    const float* X;         /* [N, T, d] contiguous */
+    const float* Y;         /* [N, ldy] labels */
+    const float* M;         /* [N, ldy] 1 = known */
+    float* q;               /* [d] attn_query */
+    float* W;               /* [L, d] */
+    float* b;               /* [L] */
+    float* mq;              /* Adam first / second moments, the shapes of q, W and b */
+    float* vq;
+    float* mW;
+    float* vW;
+    float* mb;
+    float* vb;
+    const int* perm;        /* [S * bs] this epoch's row order, device memory */
+    void* ws;               /* medp_pool_head_ws_bytes(d, L, bs) bytes */
+    double* loss_out;       /* [2] */
+    int N, T, d, L, ldy, bs, S;
+    int step0;              /* steps taken before this call */
+    double lr, weight_decay, beta1, beta2, eps;
+    float dropout_p;
+    unsigned seed, stream_id;
+    int reserved_;
+} MedpPoolHeadProblem;
+typedef struct {
+    const float* X;         /* [N, ldx] the inputs, read in place */
+    const float* Y;         /* [N, ldy] */
+    const float* M;         /* [N, ldy] */
+    float* W1;              /* [H, K] */
+    float* b1;              /* [H] */
+    float* W2;              /* [L, H] */
+    float* b2;              /* [L] */
+    float* mom;             /* Adam moments: first then second, each H K + H + L H + L floats in the order W1, b1, W2, b2 */
+    int* t;                 /* [1] steps taken so far */
+    const int* perm;        /* [S * bs] device memory */
+    const int* perm_host;   /* the same entries in host memory: checked, never read by the kernel */
+    double* loss_out;       /* [2] */
+    long long ldx;
+    int N, ldy, col0, K, H, L, bs, S, reserved0_;
+    double lr, weight_decay, beta1, beta2, eps;
+    float dropout_p;
+    unsigned seed, stream_id;
+    int reserved_;
+} MedpMlpHeadProblem;
+int medp_pool_head_rows_onchip(int T, int d);
+size_t medp_pool_head_ws_bytes(int d, int L, int bs);
+int medp_pool_head_train_epoch(const MedpPoolHeadProblem* pb, const int* perm_host, void* stream);
+int medp_pool_head_scores(const float* X, int N, int T, int d, int L, const float* q, const float* W, const float* b, const int* rows,
+                          int n, float* logits, double* probs, void* stream);
+int medp_mlp_head_supported(int K, int L, int H, int bs);
+int medp_mlp_head_train_epoch(const MedpMlpHeadProblem* table_host, const MedpMlpHeadProblem* table_dev, int P, void* stream);
+int medp_mlp_head_scores(const float* X, long long ldx, int N, int col0, int K, int H, int L, const float* W1, const float* b1,
+                         const float* W2, const float* b2, const int* rows, int n, float* logits, double* probs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

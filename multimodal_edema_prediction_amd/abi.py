@@ -69,6 +69,22 @@ class MedpHeadProblem(ctypes.Structure):
                 + [("dropout_p", F), ("seed", U), ("stream_id", U), ("reserved_", I)])
 
 
+class MedpPoolHeadProblem(ctypes.Structure):
+    """The attention-pooled head's problem (include/medp_hip.h)."""
+    _fields_ = ([(n, P) for n in ("X", "Y", "M", "q", "W", "b", "mq", "vq", "mW", "vW", "mb", "vb", "perm", "ws", "loss_out")]
+                + [(n, I) for n in ("N", "T", "d", "L", "ldy", "bs", "S", "step0")]
+                + [(n, c_double) for n in ("lr", "weight_decay", "beta1", "beta2", "eps")]
+                + [("dropout_p", F), ("seed", U), ("stream_id", U), ("reserved_", I)])
+
+
+class MedpMlpHeadProblem(ctypes.Structure):
+    """One problem of the MLP fusion head's table (include/medp_hip.h)."""
+    _fields_ = ([(n, P) for n in ("X", "Y", "M", "W1", "b1", "W2", "b2", "mom", "t", "perm", "perm_host", "loss_out")] + [("ldx", LL)]
+                + [(n, I) for n in ("N", "ldy", "col0", "K", "H", "L", "bs", "S", "reserved0_")]
+                + [(n, c_double) for n in ("lr", "weight_decay", "beta1", "beta2", "eps")]
+                + [("dropout_p", F), ("seed", U), ("stream_id", U), ("reserved_", I)])
+
+
 # name -> (restype, argtypes); must list every function declared in include/medp_hip.h (tests/test_abi.py checks)
 SIGNATURES = {
     "medp_last_error": (c_char_p, []),
@@ -185,6 +201,13 @@ SIGNATURES = {
     "medp_head_train_onchip": (I, [I, I, I, I]),
     "medp_head_train_epoch": (I, [P, P, I, P]),
     "medp_head_scores": (I, [P, LL, I, I, I, I, I, P, P, P, I, P, P, P]),
+    "medp_pool_head_rows_onchip": (I, [I, I]),
+    "medp_pool_head_ws_bytes": (SZ, [I, I, I]),
+    "medp_pool_head_train_epoch": (I, [P, P, P]),
+    "medp_pool_head_scores": (I, [P, I, I, I, I, P, P, P, P, I, P, P, P]),
+    "medp_mlp_head_supported": (I, [I, I, I, I]),
+    "medp_mlp_head_train_epoch": (I, [P, P, I, P]),
+    "medp_mlp_head_scores": (I, [P, LL, I, I, I, I, I, P, P, P, P, P, I, P, P, P]),
     "medp_rng_set_epoch_ptr": (I, [P]),
     "medp_counter_advance": (I, [P, P]),
 }

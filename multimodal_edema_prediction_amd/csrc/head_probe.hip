@@ -13,6 +13,7 @@
 //   head_scores_kernel       logits and fp32 sigmoid probabilities of a row list, the summation order of phase A.
 // fp32 in storage; fp64 accumulators; no floating-point atomics; every reduction in a fixed order.
 #include "common.h"
+#include "head_rules.h"
 #include "medp_hip.h"
 
 namespace {
@@ -20,41 +21,11 @@ namespace {
 constexpr float kNaNf = __builtin_nanf("");
 constexpr int HT_THREADS = 512, HT_WAVES = HT_THREADS / 64;
 constexpr int HS_THREADS = 256, HS_WAVES = HS_THREADS / 64, HS_ROWS = 32;   // scores: rows per workgroup
-constexpr int HEAD_LDS_BUDGET = 144 * 1024;                                  // of the CU's 160 KiB
 
-// labels padded to a compile-time count (the accumulators stay in registers)
-__host__ __device__ inline int head_lp(int L) { return L <= 2 ? 2 : L <= 8 ? 8 : 16; }
 __host__ __device__ inline long long head_nw(int F, int L, int w) { return w == 0 ? (long long)L * F : (long long)F; }
 __host__ __device__ inline long long head_g_bytes(int L, int bs) { return (long long)bs * head_lp(L) * 4; }
 __host__ __device__ inline bool head_onchip(int F, int L, int w, int bs) {
     return head_g_bytes(L, bs) + 12 * head_nw(F, L, w) <= HEAD_LDS_BUDGET;
-}
-
-// every thread gets the sum; waves are added in wave order
-__device__ __forceinline__ double block_sum_wave_order_f64(double v, double* red) {
-    v = wave_sum_f64(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < HT_WAVES; ++w) s += red[w];
-    return s;
-}
-
-struct AdamScalars {
-    float decay, omb1, beta2, omb2, step_size, bc2_sqrt, eps;
-};
-// torch.optim.AdamW, single-tensor path: mul_(1 - lr wd); lerp_(g, 1 - b1); mul_(b2).addcmul_(g, g, 1 - b2);
-// denom = sqrt(v) / sqrt(1 - b2^t) + eps; addcdiv_(m, denom, -lr / (1 - b1^t))
-__device__ __forceinline__ void adamw(float* p, float* m, float* v, float g, const AdamScalars& a) {
-    const float pn = *p * a.decay;
-    const float mn = *m + a.omb1 * (g - *m);
-    const float vn = *v * a.beta2 + (a.omb2 * g) * g;
-    const float denom = sqrtf(vn) / a.bc2_sqrt + a.eps;
-    *p = pn + (-a.step_size * mn) / denom;
-    *m = mn;
-    *v = vn;
 }
 
 // dot products of one row with every label's weights: lanes stride the columns, the result (all lanes) per label in acc[]
@@ -97,11 +68,7 @@ __device__ __forceinline__ void head_epoch(const MedpHeadProblem& pb, float* gs,
     const int t0 = pb.t[0];
     double b1t = pow(pb.beta1, (double)t0), b2t = pow(pb.beta2, (double)t0);
     AdamScalars a;
-    a.decay = (float)(1.0 - pb.lr * pb.weight_decay);
-    a.omb1 = (float)(1.0 - pb.beta1);
-    a.beta2 = (float)pb.beta2;
-    a.omb2 = (float)(1.0 - pb.beta2);
-    a.eps = (float)pb.eps;
+    adam_fixed_scalars(a, pb.lr, pb.weight_decay, pb.beta1, pb.beta2, pb.eps);
     double run_l = 0.0, run_v = 0.0;
     for (int s = 0; s < pb.S; ++s) {
         const int t = t0 + s + 1;
@@ -109,8 +76,7 @@ __device__ __forceinline__ void head_epoch(const MedpHeadProblem& pb, float* gs,
         const int* pr = pb.perm + (size_t)s * bs;
         b1t *= pb.beta1;
         b2t *= pb.beta2;
-        a.step_size = (float)(pb.lr / (1.0 - b1t));
-        a.bc2_sqrt = (float)sqrt(1.0 - b2t);
+        adam_step_scalars(a, pb.lr, b1t, b2t);
         // ---- A: logits into gs
         if (w == 0) {
             for (int r = wave; r < bs; r += HT_WAVES) {
@@ -139,7 +105,7 @@ __device__ __forceinline__ void head_epoch(const MedpHeadProblem& pb, float* gs,
         // ---- vc over the whole minibatch, then g = (sigmoid(z) - y) M / vc and the loss sum
         double part = 0.0;
         for (int e = tid; e < bs * L; e += HT_THREADS) part += (double)pb.M[(size_t)pr[e / L] * pb.ldy + e % L];
-        const double vc = block_sum_wave_order_f64(part, red);               // its barriers also publish the logits
+        const double vc = block_sum_wave_order_f64<HT_WAVES>(part, red);     // its barriers also publish the logits
         part = 0.0;
         for (int e = tid; e < bs * L; e += HT_THREADS) {
             const int r = e / L, l = e % L;
@@ -150,7 +116,7 @@ __device__ __forceinline__ void head_epoch(const MedpHeadProblem& pb, float* gs,
             const double sg = z >= 0.0 ? 1.0 / (1.0 + ex) : ex / (1.0 + ex);
             gs[r * LP + l] = vc > 0.0 ? (float)((sg - y) * m / vc) : 0.f;   // vc = 0: the reference's loss is logits.sum() * 0
         }
-        const double lsum = block_sum_wave_order_f64(part, red);             // publishes g
+        const double lsum = block_sum_wave_order_f64<HT_WAVES>(part, red);   // publishes g
         if (vc > 0.0) {
             run_l += lsum / vc * vc;
             run_v += vc;

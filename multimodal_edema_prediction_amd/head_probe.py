@@ -12,19 +12,29 @@ What runs where
                 conditional copy of (W, b) into the best slot.
   host          the initial parameters (torch's default CPU generator, the reference's order), every epoch's permutation in the
                 DataLoader's draw order, the problem tables (validated before the first launch).
-`eager_fit` is the reference's loop through torch autograd for the heads no kernel covers (learned attention pooling, the MLP
-fusion head): the same selection rule, NOT accelerated.  Without a GPU every entry point raises (no CPU fallback)."""
+The two heads with a hidden stage run on csrc/pool_head_probe.hip:
+  attention pooling  `PoolHeadProblem`, `train_pool_head`: a step is two launches (a row kernel, one workgroup per minibatch row,
+                and a column kernel that sums the rows in order and applies AdamW); `medp_pool_head_train_epoch` enqueues every step
+                of an epoch from one call.  Python counts the steps (the kernels keep no device counter).
+  MLP fusion    `MlpHeadProblem`, `train_mlp_heads`: every step of an epoch in one launch, a workgroup per problem, parameters,
+                moments and activations in LDS.
+All three trainers share one selection rule (`BestSelection`).  `eager_fit` is the reference's loop through torch autograd: the
+fallback for a shape outside the kernels' limits, and the baseline the timing tool compares with.  Without a GPU every entry point
+raises (no CPU fallback)."""
 from __future__ import annotations
 
+import ctypes
 from typing import Callable, Sequence
 
 import numpy as np
 import torch
 
-from .abi import MedpHeadProblem, check, fp32_matrix, lib, ptr, require_gpu, stream, table_bytes
+from .abi import (MedpHeadProblem, MedpMlpHeadProblem, MedpPoolHeadProblem, check, fp32_matrix, lib, ptr, require_gpu, stream,
+                  table_bytes)
 from .probe_stats import LabelMetrics, nan_mean
 
 MAX_F, MAX_L, MAX_BS = 32768, 16, 1024          # MEDP_HEAD_MAX_*
+MAX_T, MAX_K, MAX_H = 1024, 64, 1024            # MEDP_POOL_HEAD_MAX_T, MEDP_MLP_HEAD_MAX_K / _H
 BETAS, EPS = (0.9, 0.999), 1e-8                 # torch.optim.AdamW's defaults, which the reference takes
 
 
@@ -138,6 +148,48 @@ def head_scores(X, W, b, *, col0: int = 0, F: int | None = None, label_width: in
 # ------------------------------------------------------------------------------------------------------------------------------
 # the trainer
 # ------------------------------------------------------------------------------------------------------------------------------
+class BestSelection:
+    """The reference's per-epoch selection, on the device: macro AUROC of the validation probabilities (`LabelMetrics`, `nan_mean`),
+    strict `>` against the running best (NaN never wins), `torch.where` copies of every live parameter tensor into its best slot.
+    `live`: {result key: the tensor the kernels update in place}.  Nothing here synchronises; `result` is called after the run's
+    one synchronise."""
+
+    def __init__(self, epochs: int, live: dict, metrics: LabelMetrics, n_val: int, L: int, record_val_logits: bool):
+        dev = next(iter(live.values())).device
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.live, self.metrics, self.record = live, metrics, record_val_logits
+        self.curve = torch.full((epochs,), float("nan"), **f64)
+        self.best = torch.full((), -float("inf"), **f64)
+        self.best_epoch = torch.full((), -1, dtype=torch.int64, device=dev)
+        self.slots = {k: v.clone() for k, v in live.items()}
+        self.logits = torch.empty((epochs if record_val_logits else 1, n_val, L), dtype=torch.float32, device=dev)
+        self.probs = torch.empty((L, n_val), **f64)
+
+    def buffers(self, e: int):
+        """(logits [n, L], probs [L, n]) the scores kernel of epoch e writes."""
+        return self.logits[e if self.record else 0], self.probs
+
+    def update(self, e: int) -> None:
+        macro = nan_mean(self.metrics(self.probs)[:, 1])
+        better = macro > self.best                                                     # strict; NaN never wins
+        self.best = torch.where(better, macro, self.best)
+        self.best_epoch = torch.where(better, torch.full_like(self.best_epoch, e + 1), self.best_epoch)
+        for k, v in self.live.items():
+            self.slots[k] = torch.where(better, v, self.slots[k])
+        self.curve[e] = macro
+
+    def result(self, losses_h: np.ndarray) -> dict:
+        """losses_h [E, 2] host.  The result dict of the trainers."""
+        best_epoch = int(self.best_epoch.item())
+        if best_epoch < 0:
+            raise ValueError("no epoch has a defined validation macro AUROC: no label has two known validation rows of both classes")
+        res = {"curve": self.curve.cpu().numpy(), "loss_sum": losses_h[:, 0], "valid_sum": losses_h[:, 1], "best_epoch": best_epoch,
+               "best_val": float(self.best.item()), **self.slots}
+        if self.record:
+            res["val_logits"] = self.logits.cpu().numpy()
+        return res
+
+
 def train_heads(problems: Sequence[HeadProblem], vals: Sequence[tuple], epochs: int, perms: Sequence[np.ndarray],
                 record_val_logits: bool = False) -> list:
     """`epochs` epochs of every problem, one launch group per epoch, best-validation-macro-AUROC selection on the device.
@@ -163,43 +215,254 @@ def train_heads(problems: Sequence[HeadProblem], vals: Sequence[tuple], epochs: 
         if rc != 0 and b"null device table" not in lib().medp_last_error():
             check(rc, "head_train_epoch")
     tables_dev = torch.as_tensor(np.stack([t[1] for t in tables]) if E else np.zeros((0, 1), np.uint8), device=dev)
-    f64 = dict(dtype=torch.float64, device=dev)
-    state = []
+    sel = []
     for p, pb in enumerate(problems):
         n = Xv[p].shape[0]
-        state.append({"curve": torch.full((E,), float("nan"), **f64), "best": torch.full((), -float("inf"), **f64),
-                      "best_epoch": torch.full((), -1, dtype=torch.int64, device=dev), "best_W": pb.W.clone(), "best_b": pb.b.clone(),
-                      "logits": torch.empty((E if record_val_logits else 1, n, pb.L), dtype=torch.float32, device=dev),
-                      "probs": torch.empty((pb.L, n), **f64)})
+        sel.append(BestSelection(E, {"best_W": pb.W, "best_b": pb.b}, metrics[p], n, pb.L, record_val_logits))
     for e in range(E):
         check(lib().medp_head_train_epoch(tables[e][0], ptr(tables_dev[e]), P, stream()), "head_train_epoch")
         for p, pb in enumerate(problems):
-            st = state[p]
-            head_scores(Xv[p], pb.W, pb.b, col0=pb.col0, F=pb.F, label_width=pb.label_width,
-                        logits=st["logits"][e if record_val_logits else 0], probs=st["probs"])
-            macro = nan_mean(metrics[p](st["probs"])[:, 1])
-            better = macro > st["best"]                                                # strict; NaN never wins
-            st["best"] = torch.where(better, macro, st["best"])
-            st["best_epoch"] = torch.where(better, torch.full_like(st["best_epoch"], e + 1), st["best_epoch"])
-            st["best_W"] = torch.where(better, pb.W, st["best_W"])
-            st["best_b"] = torch.where(better, pb.b, st["best_b"])
-            st["curve"][e] = macro
+            logits, probs = sel[p].buffers(e)
+            head_scores(Xv[p], pb.W, pb.b, col0=pb.col0, F=pb.F, label_width=pb.label_width, logits=logits, probs=probs)
+            sel[p].update(e)
     torch.cuda.synchronize(dev)
     losses_h = losses.cpu().numpy()
     out = []
     for p, pb in enumerate(problems):
-        st = state[p]
         if np.isnan(losses_h[:, p]).any():
             raise ValueError(f"train_heads: problem {p} has a permutation entry outside [0, {pb.N})")
-        best_epoch = int(st["best_epoch"].item())
-        if best_epoch < 0:
-            raise ValueError("no epoch has a defined validation macro AUROC: no label has two known validation rows of both classes")
-        res = {"curve": st["curve"].cpu().numpy(), "loss_sum": losses_h[:, p, 0], "valid_sum": losses_h[:, p, 1], "best_epoch": best_epoch,
-               "best_val": float(st["best"].item()), "best_W": st["best_W"], "best_b": st["best_b"]}
-        if record_val_logits:
-            res["val_logits"] = st["logits"].cpu().numpy()
-        out.append(res)
+        out.append(sel[p].result(losses_h[:, p]))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# heads with a hidden stage: attention pooling, the MLP fusion head (csrc/pool_head_probe.hip)
+# ------------------------------------------------------------------------------------------------------------------------------
+def pool_head_supported(T: int, d: int, L: int, bs: int) -> bool:
+    """The limits of `medp_pool_head_train_epoch` (needs no GPU)."""
+    return 1 <= T <= MAX_T and 1 <= d <= MAX_F and 1 <= L <= MAX_L and 1 <= bs <= MAX_BS
+
+
+def pool_rows_onchip(T: int, d: int) -> bool:
+    """True when the row kernel keeps a row's T d tokens in LDS; they are re-read from global memory otherwise."""
+    return bool(lib().medp_pool_head_rows_onchip(int(T), int(d)))
+
+
+def mlp_head_supported(L: int, H: int, bs: int, K: int | None = None) -> bool:
+    """True when the MLP head's parameters, moments and minibatch activations fit the LDS budget (K inputs, 2 L by default)."""
+    return bool(lib().medp_mlp_head_supported(int(2 * L if K is None else K), int(L), int(H), int(bs)))
+
+
+def _perm_pair(perm, count: int, dev):
+    """(host int32 array of `count` entries, its device copy): the kernels read the copy of exactly what the library validates."""
+    host = np.ascontiguousarray(np.asarray(perm.cpu() if isinstance(perm, torch.Tensor) else perm).reshape(-1)[:count], dtype=np.int32)
+    if host.size < count:
+        raise ValueError(f"a permutation has {host.size} entries, {count} are needed")
+    return host, (torch.as_tensor(host, device=dev) if dev is not None else None)
+
+
+class PoolHeadProblem:
+    """`LinearHead(use_attn_pool=True)` over X [N, T, d]: attn_query q [d], head.1.weight W [L, d], head.1.bias b [L].  Parameters,
+    Adam moments and the workspace live on the device; `steps` (host) counts the steps taken."""
+
+    def __init__(self, X, Y, M, q, W, b, *, bs: int = 128, lr: float = 1e-4, weight_decay: float = 1e-4, dropout: float = 0.0, seed: int = 0,
+                 stream_id: int = 0, betas=BETAS, eps: float = EPS):
+        if X.dtype != torch.float32 or X.ndim != 3:
+            raise TypeError("PoolHeadProblem: X is fp32 [N, T, d]")
+        self.X = X.contiguous()
+        self.N, self.T, self.d = (int(v) for v in self.X.shape)
+        self.Y, ny, self.ldy = fp32_matrix(Y, "Y")
+        self.M, nm, ldm = fp32_matrix(M, "M")
+        if ny != self.N or nm != self.N or ldm != self.ldy:
+            raise ValueError(f"PoolHeadProblem: X has {self.N} rows, Y {ny} x {self.ldy}, M {nm} x {ldm}")
+        dev = self.X.device
+        own = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous().clone()  # noqa: E731
+        self.q, self.W, self.b = own(q), own(W), own(b)
+        self.L = int(self.b.numel())
+        if self.q.numel() != self.d or self.W.numel() != self.L * self.d:
+            raise ValueError(f"PoolHeadProblem: q has {self.q.numel()} and W {self.W.numel()} elements, d={self.d}, L={self.L}")
+        self.mq, self.vq, self.mW, self.vW, self.mb, self.vb = (torch.zeros_like(t) for t in (self.q, self.q, self.W, self.W, self.b, self.b))
+        self.bs, self.S, self.steps = int(bs), self.N // max(int(bs), 1), 0
+        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
+        self.dropout, self.seed, self.stream_id = float(dropout), int(seed) & 0xFFFFFFFF, int(stream_id) & 0xFFFFFFFF
+        nbytes = int(lib().medp_pool_head_ws_bytes(self.d, min(max(self.L, 1), MAX_L), max(self.bs, 1)))
+        self.ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev) if self.X.is_cuda else None
+
+    def live(self) -> dict:
+        return {"attn_query": self.q, "head.1.weight": self.W, "head.1.bias": self.b}
+
+    def entry(self, perm_dev, loss_out, addr=ptr) -> MedpPoolHeadProblem:
+        a = addr
+        return MedpPoolHeadProblem(a(self.X), a(self.Y), a(self.M), a(self.q), a(self.W), a(self.b), a(self.mq), a(self.vq), a(self.mW),
+                                   a(self.vW), a(self.mb), a(self.vb), a(perm_dev), a(self.ws), a(loss_out), self.N, self.T, self.d, self.L,
+                                   self.ldy, self.bs, self.S, self.steps, self.lr, self.weight_decay, self.betas[0], self.betas[1], self.eps,
+                                   self.dropout, self.seed, self.stream_id, 0)
+
+
+def pool_head_train_epoch(pb: PoolHeadProblem, perm, loss_out: torch.Tensor | None = None) -> torch.Tensor:
+    """One epoch (S steps, two launches each) enqueued by ONE library call.  perm: at least S bs row indices (host array or tensor);
+    the device copy is made from the host array the library validates.  Returns loss_out [2] fp64 = (sum of loss * vc, sum of vc);
+    parameters and moments are updated in place and pb.steps advances by S."""
+    require_gpu()
+    host, dev_perm = _perm_pair(perm, pb.S * pb.bs, pb.X.device)
+    if loss_out is None:
+        loss_out = torch.empty(2, dtype=torch.float64, device=pb.X.device)
+    entry = pb.entry(dev_perm, loss_out)
+    check(lib().medp_pool_head_train_epoch(ctypes.byref(entry), host.ctypes.data, stream()), "pool_head_train_epoch")
+    pb.steps += pb.S
+    return loss_out
+
+
+def pool_head_scores(X, q, W, b, *, rows: torch.Tensor | None = None, logits=None, probs=None):
+    """(logits [n, L] fp32, probs [L, n] fp64 = the fp32 sigmoid widened) of the attention-pooled head over X [N, T, d]."""
+    require_gpu()
+    if X.dtype != torch.float32 or X.ndim != 3:
+        raise TypeError("pool_head_scores: X is fp32 [N, T, d]")
+    X = X.contiguous()
+    N, T, d = (int(v) for v in X.shape)
+    L = int(b.numel())
+    n = N if rows is None else int(rows.numel())
+    if rows is not None and rows.dtype != torch.int32:
+        raise TypeError("pool_head_scores: rows are int32")
+    if any(t.dtype != torch.float32 for t in (q, W, b)) or q.numel() != d or W.numel() != L * d:
+        raise ValueError("pool_head_scores: q fp32 [d], W fp32 [L, d], b fp32 [L]")
+    logits = torch.empty((n, L), dtype=torch.float32, device=X.device) if logits is None else logits
+    probs = torch.empty((L, n), dtype=torch.float64, device=X.device) if probs is None else probs
+    check(lib().medp_pool_head_scores(ptr(X), N, T, d, L, ptr(q.contiguous()), ptr(W.contiguous()), ptr(b.contiguous()), ptr(rows), n,
+                                      ptr(logits), ptr(probs), stream()), "pool_head_scores")
+    return logits, probs
+
+
+class MlpHeadProblem:
+    """`LogitFusionHead("mlp")` over the K columns [col0, col0 + K) of X: head.0.weight W1 [H, K], head.0.bias b1 [H], head.3.weight
+    W2 [L, H], head.3.bias b2 [L].  Parameters, Adam moments (one buffer: first then second, in the order W1, b1, W2, b2) and the step
+    count live on the device."""
+
+    def __init__(self, X, Y, M, W1, b1, W2, b2, *, col0: int = 0, K: int | None = None, bs: int = 128, lr: float = 1e-3,
+                 weight_decay: float = 1e-4, dropout: float = 0.0, seed: int = 0, stream_id: int = 0, betas=BETAS, eps: float = EPS):
+        self.X, self.N, self.ldx = fp32_matrix(X, "X")
+        self.Y, ny, self.ldy = fp32_matrix(Y, "Y")
+        self.M, nm, ldm = fp32_matrix(M, "M")
+        if ny != self.N or nm != self.N or ldm != self.ldy:
+            raise ValueError(f"MlpHeadProblem: X has {self.N} rows, Y {ny} x {self.ldy}, M {nm} x {ldm}")
+        dev = self.X.device
+        own = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous().clone()  # noqa: E731
+        self.W1, self.b1, self.W2, self.b2 = own(W1), own(b1), own(W2), own(b2)
+        self.col0 = int(col0)
+        self.K = int(K) if K is not None else self.ldx - self.col0
+        self.H, self.L = int(self.b1.numel()), int(self.b2.numel())
+        if self.W1.numel() != self.H * self.K or self.W2.numel() != self.L * self.H:
+            raise ValueError(f"MlpHeadProblem: W1 has {self.W1.numel()} and W2 {self.W2.numel()} elements, K={self.K}, H={self.H}, L={self.L}")
+        self.n_params = self.H * self.K + self.H + self.L * self.H + self.L
+        self.mom = torch.zeros(2 * self.n_params, dtype=torch.float32, device=dev)
+        self.t = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.bs, self.S = int(bs), self.N // max(int(bs), 1)
+        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
+        self.dropout, self.seed, self.stream_id = float(dropout), int(seed) & 0xFFFFFFFF, int(stream_id) & 0xFFFFFFFF
+
+    def live(self) -> dict:
+        return {"head.0.weight": self.W1, "head.0.bias": self.b1, "head.3.weight": self.W2, "head.3.bias": self.b2}
+
+    def entry(self, perm_dev, perm_host: np.ndarray, loss_out, addr=ptr) -> MedpMlpHeadProblem:
+        a = addr
+        return MedpMlpHeadProblem(a(self.X), a(self.Y), a(self.M), a(self.W1), a(self.b1), a(self.W2), a(self.b2), a(self.mom), a(self.t),
+                                  a(perm_dev), None if perm_host is None else perm_host.ctypes.data, a(loss_out), self.ldx, self.N, self.ldy,
+                                  self.col0, self.K, self.H, self.L, self.bs, self.S, 0, self.lr, self.weight_decay, self.betas[0],
+                                  self.betas[1], self.eps, self.dropout, self.seed, self.stream_id, 0)
+
+
+def make_mlp_table(entries: Sequence[MedpMlpHeadProblem]):
+    """(host ctypes array, the same bytes as a uint8 numpy array)."""
+    host = (MedpMlpHeadProblem * max(len(entries), 1))(*entries)
+    return host, table_bytes(host, len(entries))
+
+
+def mlp_head_train_epoch(problems: Sequence[MlpHeadProblem], perms: Sequence, loss_out: torch.Tensor | None = None) -> torch.Tensor:
+    """One epoch of every problem in ONE launch.  perms[p]: at least S bs row indices (host array or tensor).  Returns loss_out [P, 2]."""
+    require_gpu()
+    dev = problems[0].X.device
+    if loss_out is None:
+        loss_out = torch.empty((len(problems), 2), dtype=torch.float64, device=dev)
+    pairs = [_perm_pair(pm, pb.S * pb.bs, dev) for pb, pm in zip(problems, perms)]
+    host, raw = make_mlp_table([pb.entry(pd, ph, loss_out[p]) for p, (pb, (ph, pd)) in enumerate(zip(problems, pairs))])
+    table_dev = torch.as_tensor(raw, device=dev)
+    check(lib().medp_mlp_head_train_epoch(host, ptr(table_dev), len(problems), stream()), "mlp_head_train_epoch")
+    return loss_out
+
+
+def mlp_head_scores(X, W1, b1, W2, b2, *, col0: int = 0, K: int | None = None, rows: torch.Tensor | None = None, logits=None, probs=None):
+    """(logits [n, L] fp32, probs [L, n] fp64 = the fp32 sigmoid widened) of the MLP head, no dropout."""
+    require_gpu()
+    X, N, ldx = fp32_matrix(X, "X")
+    H, L = int(b1.numel()), int(b2.numel())
+    K = ldx - col0 if K is None else K
+    n = N if rows is None else int(rows.numel())
+    if rows is not None and rows.dtype != torch.int32:
+        raise TypeError("mlp_head_scores: rows are int32")
+    if any(t.dtype != torch.float32 for t in (W1, b1, W2, b2)) or W1.numel() != H * K or W2.numel() != L * H:
+        raise ValueError("mlp_head_scores: W1 fp32 [H, K], b1 fp32 [H], W2 fp32 [L, H], b2 fp32 [L]")
+    logits = torch.empty((n, L), dtype=torch.float32, device=X.device) if logits is None else logits
+    probs = torch.empty((L, n), dtype=torch.float64, device=X.device) if probs is None else probs
+    check(lib().medp_mlp_head_scores(ptr(X), ldx, N, int(col0), int(K), H, L, ptr(W1.contiguous()), ptr(b1.contiguous()), ptr(W2.contiguous()),
+                                     ptr(b2.contiguous()), ptr(rows), n, ptr(logits), ptr(probs), stream()), "mlp_head_scores")
+    return logits, probs
+
+
+def _epoch_perms(perms, E: int, count: int, who: str) -> np.ndarray:
+    host = np.ascontiguousarray(np.asarray(perms)[:, :count], dtype=np.int32)
+    if host.shape != (E, count):
+        raise ValueError(f"{who}: [{E}, {count}] permutation entries are needed, got {tuple(host.shape)}")
+    return host
+
+
+def train_pool_head(pb: PoolHeadProblem, val: tuple, epochs: int, perms: np.ndarray, record_val_logits: bool = False) -> dict:
+    """`train_heads` for the attention-pooled head: per epoch one `medp_pool_head_train_epoch` call and one scores launch, the
+    selection of `BestSelection`, one synchronise at the end.  val = (X_va [n, T, d], Y_va, M_va); perms [epochs, >= S bs].
+    The result dict of `train_heads` with the best `attn_query`, `head.1.weight`, `head.1.bias` in place of best_W / best_b."""
+    require_gpu()
+    E, dev = int(epochs), pb.X.device
+    metrics = LabelMetrics(val[1].to(dev), val[2].to(dev))                             # raises before the first launch
+    Xv = val[0].to(dev).contiguous()
+    host = _epoch_perms(perms, E, pb.S * pb.bs, "train_pool_head")
+    perm_dev = torch.as_tensor(host, device=dev)                                       # every epoch's row order in one copy
+    losses = torch.zeros((E, 2), dtype=torch.float64, device=dev)
+    sel = BestSelection(E, pb.live(), metrics, Xv.shape[0], pb.L, record_val_logits)
+    for e in range(E):
+        entry = pb.entry(perm_dev[e], losses[e])
+        check(lib().medp_pool_head_train_epoch(ctypes.byref(entry), host[e].ctypes.data, stream()), "pool_head_train_epoch")
+        pb.steps += pb.S
+        logits, probs = sel.buffers(e)
+        pool_head_scores(Xv, pb.q, pb.W, pb.b, logits=logits, probs=probs)
+        sel.update(e)
+    torch.cuda.synchronize(dev)
+    return sel.result(losses.cpu().numpy())
+
+
+def train_mlp_heads(problems: Sequence[MlpHeadProblem], vals: Sequence[tuple], epochs: int, perms: Sequence[np.ndarray],
+                    record_val_logits: bool = False) -> list:
+    """`train_heads` for MLP fusion heads: one launch per epoch serves every problem.  vals[p] = (X_va, Y_va, M_va) with the problem's
+    column layout.  The result dicts carry the best `head.0.weight`, `head.0.bias`, `head.3.weight`, `head.3.bias`."""
+    require_gpu()
+    P, E = len(problems), int(epochs)
+    dev = problems[0].X.device
+    metrics = [LabelMetrics(v[1].to(dev), v[2].to(dev)) for v in vals]                 # raises before the first launch
+    Xv = [fp32_matrix(v[0].to(dev), "X_va")[0] for v in vals]
+    hosts = [_epoch_perms(pm, E, pb.S * pb.bs, "train_mlp_heads") for pb, pm in zip(problems, perms)]
+    perm_dev = [torch.as_tensor(h, device=dev) for h in hosts]
+    losses = torch.zeros((E, P, 2), dtype=torch.float64, device=dev)
+    # every epoch's table up front: the loop copies nothing to or from the device
+    tables = [make_mlp_table([pb.entry(perm_dev[p][e], hosts[p][e], losses[e, p]) for p, pb in enumerate(problems)]) for e in range(E)]
+    tables_dev = torch.as_tensor(np.stack([t[1] for t in tables]) if E else np.zeros((0, 1), np.uint8), device=dev)
+    sel = [BestSelection(E, pb.live(), metrics[p], Xv[p].shape[0], pb.L, record_val_logits) for p, pb in enumerate(problems)]
+    for e in range(E):
+        check(lib().medp_mlp_head_train_epoch(tables[e][0], ptr(tables_dev[e]), P, stream()), "mlp_head_train_epoch")
+        for p, pb in enumerate(problems):
+            logits, probs = sel[p].buffers(e)
+            mlp_head_scores(Xv[p], pb.W1, pb.b1, pb.W2, pb.b2, col0=pb.col0, K=pb.K, logits=logits, probs=probs)
+            sel[p].update(e)
+    torch.cuda.synchronize(dev)
+    losses_h = losses.cpu().numpy()
+    return [sel[p].result(losses_h[:, p]) for p in range(P)]
 
 
 def history_lines(result: dict, tag: str = "epoch") -> list:
@@ -209,7 +472,7 @@ def history_lines(result: dict, tag: str = "epoch") -> list:
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# eager fallback (not accelerated)
+# eager fallback and comparison baseline
 # ------------------------------------------------------------------------------------------------------------------------------
 def masked_bce_loss(logits: torch.Tensor, labels: torch.Tensor, label_mask: torch.Tensor) -> torch.Tensor:
     """Mean BCE-with-logits over the known labels of the batch; an all-unknown batch gives a zero that still has a graph."""
@@ -223,9 +486,10 @@ def masked_bce_loss(logits: torch.Tensor, labels: torch.Tensor, label_mask: torc
 
 def eager_fit(model: torch.nn.Module, forward: Callable, train: Sequence[torch.Tensor], Y_tr, M_tr, val: Sequence[torch.Tensor], Y_va, M_va,
               *, epochs: int, batch_size: int, lr: float, weight_decay: float, perms: np.ndarray) -> dict:
-    """The reference's loop through torch autograd on the device, for the heads no kernel covers: `forward(model, *inputs)` gives the
-    logits; minibatches follow `perms`; AdamW; per epoch the validation macro AUROC from the metrics kernel and the strict `>`
-    selection.  Synchronises every step, as the reference does (`.item()`): this path is NOT accelerated."""
+    """The reference's loop through torch autograd on the device, for a head whose shape is outside the kernels' limits, and the
+    baseline the device paths are timed against: `forward(model, *inputs)` gives the logits; minibatches follow `perms`; AdamW; per
+    epoch the validation macro AUROC from the metrics kernel and the strict `>` selection.  Synchronises every step, as the
+    reference does (`.item()`)."""
     require_gpu()
     dev = Y_tr.device
     opt = torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)

@@ -9,7 +9,10 @@ The reference's names, positional signatures and state-dict keys.  Stages 1 and 
     linear     a dense problem on cat(img, ts) [N, 2L], no dropout          (head.weight / head.bias)
     per_label  label_width = 2 on the interleaved [N, L, 2] layout, initialised w_img = 1, w_ts = 0, b = 0
                (per_label_w / per_label_b)
-    mlp        no kernel: the eager loop of `head_probe.eager_fit`, NOT accelerated (as is a `duett_attn_pool` stage 2).
+    mlp        its own kernel, every step of an epoch in one launch (`head_probe.train_mlp_heads`) on cat(img, ts) [N, 2L]
+               (head.0.weight / head.0.bias / head.3.weight / head.3.bias); `eager=True`, or a hidden width beyond the LDS budget,
+               runs the torch loop of `head_probe.eager_fit`.
+A `duett_attn_pool` stage 2 trains on the attention-pool kernels through `train_linear_head`.
 `main()` runs on `SyntheticCohort` with the synthetic encoders.  Without a GPU the trainers raise (no CPU fallback)."""
 from __future__ import annotations
 
@@ -62,28 +65,42 @@ def _fusion_inputs(img: torch.Tensor, ts: torch.Tensor, fusion_type: str) -> tor
 
 def train_fusion_head(img_tr, ts_tr, Y_tr, M_tr, img_va, ts_va, Y_va, M_va, label_names, device, fusion_type: str = "linear",
                       hidden: int = 32, dropout: float = 0.1, epochs: int = 300, batch_size: int = 128, lr: float = 1e-3,
-                      weight_decay: float = 1e-4, verbose: bool = True, *, seed: int = 0, history=None, init_state=None):
+                      weight_decay: float = 1e-4, verbose: bool = True, *, seed: int = 0, history=None, init_state=None,
+                      eager: bool | None = None):
     """Fusion head on the two heads' logits -> (model on the device with the best-validation-macro-AUROC state, best epoch, value).
-    Keyword-only extras as in `train_linear_head`."""
+    Keyword-only extras as in `train_linear_head`; `eager` concerns the mlp head alone."""
     L = len(label_names)
     model = LogitFusionHead(n_labels=L, fusion_type=fusion_type, hidden=hidden, dropout=dropout)
     if init_state is not None:
         model.load_state_dict(init_state)
     if fusion_type == "mlp":
-        return _train_eager(model, lambda m, a, b: m(a, b), [img_tr, ts_tr], Y_tr, M_tr, [img_va, ts_va], Y_va, M_va, device, epochs,
-                            batch_size, lr, weight_decay, verbose, history, tag="ep")
+        N = img_tr.shape[0]
+        supported = (2 * L <= head_probe.MAX_K and 1 <= batch_size <= N and head_probe.mlp_head_supported(L, hidden, batch_size))
+        if eager is False and not supported:
+            raise ValueError(f"train_fusion_head: L={L}, hidden={hidden}, batch_size={batch_size}, N={N} is outside the mlp kernel's limits "
+                             f"(2 L <= {head_probe.MAX_K}, batch_size <= N, parameters and activations within the LDS budget)")
+        if eager or not supported:
+            return _train_eager(model, lambda m, a, b: m(a, b), [img_tr, ts_tr], Y_tr, M_tr, [img_va, ts_va], Y_va, M_va, device, epochs,
+                                batch_size, lr, weight_decay, verbose, history, tag="ep")
     require_gpu()
     device = torch.device(device)
     to = lambda t: torch.as_tensor(t).to(device).float()  # noqa: E731
     perms = head_probe.draw_epoch_permutations(img_tr.shape[0], epochs)
-    W, b, width = ((model.per_label_w, model.per_label_b, 2) if fusion_type == "per_label" else (model.head.weight, model.head.bias, 0))
-    problem = head_probe.HeadProblem(_fusion_inputs(to(img_tr), to(ts_tr), fusion_type), to(Y_tr), to(M_tr), W, b, label_width=width,
-                                     bs=batch_size, lr=lr, weight_decay=weight_decay, dropout=0.0, seed=seed)
+    record = bool(history is not None and history.get("record_val_logits"))
     val = (_fusion_inputs(to(img_va), to(ts_va), fusion_type), to(Y_va), to(M_va))
-    res = head_probe.train_heads([problem], [val], epochs, [perms],
-                                 record_val_logits=bool(history is not None and history.get("record_val_logits")))[0]
-    keys = ("per_label_w", "per_label_b") if fusion_type == "per_label" else ("head.weight", "head.bias")
-    model.load_state_dict({keys[0]: res["best_W"].reshape(W.shape), keys[1]: res["best_b"]})
+    if fusion_type == "mlp":
+        l0, l3 = model.head[0], model.head[3]
+        problem = head_probe.MlpHeadProblem(_fusion_inputs(to(img_tr), to(ts_tr), fusion_type), to(Y_tr), to(M_tr), l0.weight, l0.bias,
+                                            l3.weight, l3.bias, bs=batch_size, lr=lr, weight_decay=weight_decay, dropout=dropout, seed=seed)
+        res = head_probe.train_mlp_heads([problem], [val], epochs, [perms], record_val_logits=record)[0]
+        model.load_state_dict({k: res[k] for k in problem.live()})
+    else:
+        W, b, width = ((model.per_label_w, model.per_label_b, 2) if fusion_type == "per_label" else (model.head.weight, model.head.bias, 0))
+        problem = head_probe.HeadProblem(_fusion_inputs(to(img_tr), to(ts_tr), fusion_type), to(Y_tr), to(M_tr), W, b, label_width=width,
+                                         bs=batch_size, lr=lr, weight_decay=weight_decay, dropout=0.0, seed=seed)
+        res = head_probe.train_heads([problem], [val], epochs, [perms], record_val_logits=record)[0]
+        keys = ("per_label_w", "per_label_b") if fusion_type == "per_label" else ("head.weight", "head.bias")
+        model.load_state_dict({keys[0]: res["best_W"].reshape(W.shape), keys[1]: res["best_b"]})
     model.to(device)
     _report(res, history, verbose, tag="ep")
     return model, res["best_epoch"], res["best_val"]

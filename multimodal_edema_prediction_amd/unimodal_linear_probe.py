@@ -9,8 +9,10 @@ The reference's names, positional signatures and state-dict keys.  What differs:
   * `train_linear_head` runs every step of an epoch in one `medp_head_train_epoch` launch and selects on the device (head_probe.py);
     the initial parameters and every epoch's row order are drawn on the host exactly as the reference's module and DataLoader
     draw them, the dropout masks come from the library's counter hash (`seed`);
-  * `duett_attn_pool` (a learned attention pooling over [N, T, d]) has no kernel: it runs the reference's eager loop through torch
-    autograd on the device (`head_probe.eager_fit`), NOT accelerated;
+  * `duett_attn_pool` (a learned attention pooling over [N, T, d]) trains on its own kernels (`head_probe.train_pool_head`: a row
+    kernel and a column kernel per step, every step of an epoch enqueued by one library call) and is scored by
+    `medp_pool_head_scores`; `eager=True` runs the reference's loop through torch autograd instead (`head_probe.eager_fit`), which
+    is also what a shape outside the kernels' limits falls back to;
   * `main()` runs on `SyntheticCohort` with the synthetic encoders, as train_synthetic does (the MIMIC files are not available).
 Without a GPU the trainers raise (no CPU fallback)."""
 from __future__ import annotations
@@ -121,14 +123,19 @@ def masked_bce(logits: torch.Tensor, labels: torch.Tensor, label_mask: torch.Ten
 
 @torch.no_grad()
 def _scores(model, X: torch.Tensor, device):
-    """([N, L] fp32 logits, [N, L] fp32 probabilities) on the device: the scores kernel for a plain `Dropout -> Linear` head, the
-    module's forward (and 1 / (1 + exp(-z)) in fp32) otherwise."""
+    """([N, L] fp32 logits, [N, L] fp32 probabilities) on the device: the scores kernels for a `LinearHead` (plain or attention-pooled,
+    within the kernels' limits), the module's forward (and 1 / (1 + exp(-z)) in fp32) otherwise."""
     model.eval()
     X = X.to(device)
-    if isinstance(model, LinearHead) and not model.use_attn_pool:
+    if isinstance(model, LinearHead):
         lin = model.head[1]
-        z, p = head_probe.head_scores(X.float(), lin.weight.detach().float(), lin.bias.detach().float())
-        return z, p.t().float()                                                        # the kernel's fp32 sigmoid, widened: exact back
+        W, b = lin.weight.detach().float(), lin.bias.detach().float()
+        if not model.use_attn_pool:
+            z, p = head_probe.head_scores(X.float(), W, b)
+            return z, p.t().float()                                                    # the kernel's fp32 sigmoid, widened: exact back
+        if head_probe.pool_head_supported(X.shape[1], X.shape[2], b.numel(), 1):
+            z, p = head_probe.pool_head_scores(X.float(), model.attn_query.detach().float(), W, b)
+            return z, p.t().float()
     z = torch.cat([model(X[i:i + 512]).float() for i in range(0, X.shape[0], 512)])
     return z, 1.0 / (1.0 + torch.exp(-z))
 
@@ -218,7 +225,7 @@ def train_linear_heads(X_trs: Sequence[torch.Tensor], Y_tr, M_tr, X_vas: Sequenc
 
 
 def _train_eager(model, forward, train, Y_tr, M_tr, val, Y_va, M_va, device, epochs, batch_size, lr, weight_decay, verbose, history, tag="epoch"):
-    """The shared eager path (attention pooling, the MLP fusion head): NOT accelerated."""
+    """The shared eager path (attention pooling, the MLP fusion head): `eager=True`, or a shape outside the kernels' limits."""
     require_gpu()
     device = torch.device(device)
     perms = head_probe.draw_epoch_permutations(Y_tr.shape[0], epochs)
@@ -232,18 +239,40 @@ def _train_eager(model, forward, train, Y_tr, M_tr, val, Y_va, M_va, device, epo
 
 def train_linear_head(X_tr, Y_tr, M_tr, X_va, Y_va, M_va, label_names: list, device, epochs: int = 100, batch_size: int = 128,
                       lr: float = 1e-4, weight_decay: float = 1e-4, dropout: float = 0.1, verbose: bool = True, use_attn_pool: bool = False,
-                      *, seed: int = 0, history=None, init_state=None):
+                      *, seed: int = 0, history=None, init_state=None, eager: bool | None = None):
     """Joint multi-label linear head -> (model on the device with the best-validation-macro-AUROC state, best epoch, best value).
     X_*: [N, d] (or [N, T, d] with use_attn_pool); Y_*: [N, L] with unknown labels as 0; M_*: [N, L], 1 = known.
     seed: the dropout hash's seed; history: a dict that receives `curve`, `train_loss`, `loss_sum`, `valid_sum` per epoch (and
     `val_logits` when it holds record_val_logits=True); init_state: a state dict loaded in place of the default initialisation.
+    eager (attention pooling only): None = the kernels when the shape is within their limits and the torch loop otherwise; True
+    forces the torch loop; False raises ValueError for a shape outside the limits.
     verbose prints the reference's per-epoch lines after the run (the epoch loop never synchronises)."""
     if use_attn_pool:
-        model = LinearHead(X_tr.shape[-1], len(label_names), dropout=dropout, use_attn_pool=True)
+        T, d, L = int(X_tr.shape[1]), int(X_tr.shape[2]), len(label_names)
+        supported = X_tr.ndim == 3 and head_probe.pool_head_supported(T, d, L, batch_size) and X_tr.shape[0] >= batch_size
+        if eager is False and not supported:
+            raise ValueError(f"train_linear_head: T={T}, d={d}, L={L}, batch_size={batch_size}, N={X_tr.shape[0]} is outside the "
+                             f"attention-pool kernels' limits (T <= {head_probe.MAX_T}, d <= {head_probe.MAX_F}, L <= {head_probe.MAX_L}, "
+                             f"batch_size <= min(N, {head_probe.MAX_BS}))")
+        model = LinearHead(d, L, dropout=dropout, use_attn_pool=True)      # attn_query is drawn before the nn.Linear, as the reference does
         if init_state is not None:
             model.load_state_dict(init_state)
-        return _train_eager(model, lambda m, x: m(x), [X_tr], Y_tr, M_tr, [X_va], Y_va, M_va, device, epochs, batch_size, lr, weight_decay,
-                            verbose, history)
+        if eager or not supported:
+            return _train_eager(model, lambda m, x: m(x), [X_tr], Y_tr, M_tr, [X_va], Y_va, M_va, device, epochs, batch_size, lr, weight_decay,
+                                verbose, history)
+        require_gpu()
+        device = torch.device(device)
+        to = lambda t: torch.as_tensor(t).to(device).float()  # noqa: E731
+        perms = head_probe.draw_epoch_permutations(X_tr.shape[0], epochs)
+        lin = model.head[1]
+        problem = head_probe.PoolHeadProblem(to(X_tr), to(Y_tr), to(M_tr), model.attn_query, lin.weight, lin.bias, bs=batch_size, lr=lr,
+                                             weight_decay=weight_decay, dropout=dropout, seed=seed)
+        res = head_probe.train_pool_head(problem, (to(X_va), to(Y_va), to(M_va)), epochs, perms,
+                                         record_val_logits=bool(history is not None and history.get("record_val_logits")))
+        model.load_state_dict({k: res[k] for k in ("attn_query", "head.1.weight", "head.1.bias")})
+        model.to(device)
+        _report(res, history, verbose)
+        return model, res["best_epoch"], res["best_val"]
     return train_linear_heads([X_tr], Y_tr, M_tr, [X_va], Y_va, M_va, label_names, device, epochs, batch_size, lr, weight_decay, dropout,
                               verbose, seed=seed, histories=[history], init_states=[init_state])[0]
 
@@ -274,7 +303,7 @@ def parse_args(argv=None):
     p.add_argument("--modality", choices=["cxr", "duett", "duett_rep", "duett_hourly_mean", "duett_multiscale", "duett_attn_pool"],
                    required=True, help="cxr: CLS token / duett_rep: [REP] token / duett_hourly_mean: mean of the hourly tokens / "
                                        "duett_multiscale: three window means and REP / duett_attn_pool: hourly tokens with a learned "
-                                       "attention pooling (eager, not accelerated); 'duett' = duett_rep")
+                                       "attention pooling; 'duett' = duett_rep")
     _cohort_args(p)
     p.add_argument("--save_features", type=str, default="", help="a folder that receives X_<modality>_<split>.npy / y_<modality>_<split>.npy")
     p.add_argument("--epochs", type=int, default=300)
