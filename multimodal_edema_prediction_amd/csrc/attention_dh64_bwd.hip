@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dh64_kernel(const BwdParams p
     else wave_body<DKV, 0>(p, smem, own0, b, h, tid, wave);     // idle wave: staging share and barriers only
 }
 
-// D[b,h,s] = <dO[b,s,h,:], O[b,s,h,:]> and the bf16 copy of dO the MFMAs read: 16 lanes per (row, head), float4 each
+// The bf16 copy of dO the MFMAs read and D[b,h,s] = <bf16(dO[b,s,h,:]), O[b,s,h,:]>: 16 lanes per (row, head), float4 each
 __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const float* __restrict__ dof, int lddof, const bf16_t* __restrict__ o, int ldo,
                                                             bf16_t* __restrict__ dob, int lddob, float* __restrict__ dsum, int B, int S,
                                                             int H) {
@@ -206,7 +206,11 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const float* __restr
     w.x = pack_bf2(g.x, g.y);
     w.y = pack_bf2(g.z, g.w);
     *(uint2*)(dob + (size_t)m * lddob + hh * 64 + l16 * 4) = w;
-    float s = (g.x * o0 + g.y * o1) + (g.z * o2 + g.w * o3);
+    // D from the ROUNDED dO, the operand dP = dO V^T is made of: dS = P o (dP - D) then has row sums that vanish up to rounding.  With
+    // the fp32 dO here, dQ and dK carried noise of order 2^-9 |dO| |V| scale |Q| that grew with the sharpness of the softmax.
+    const float g0 = __uint_as_float(w.x << 16), g1 = __uint_as_float(w.x & 0xffff0000u);
+    const float g2 = __uint_as_float(w.y << 16), g3 = __uint_as_float(w.y & 0xffff0000u);
+    float s = (g0 * o0 + g1 * o1) + (g2 * o2 + g3 * o3);
     s += __shfl_xor(s, 1, 64);
     s += __shfl_xor(s, 2, 64);
     s += __shfl_xor(s, 4, 64);
