@@ -11,14 +11,15 @@
 //     for the whole epoch when they fit (head_onchip), in global memory (a few hundred KB: L2-resident) otherwise; b and its
 //     moments (<= 16 values) stay in global memory.  No workgroup waits for another.
 //   head_scores_kernel       logits and fp32 sigmoid probabilities of a row list, the summation order of phase A.
-// fp32 in storage; fp64 accumulators; no floating-point atomics; every reduction in a fixed order.
+// fp32 in storage; fp64 accumulators; no floating-point atomics; every reduction in a fixed order.  What a head has in common with
+// those of pool_head_probe.hip (step clock, AdamW, masked BCE, loss sums, score store, label-padding dispatch, the launchers' checks
+// of steps and columns) is head_rules.h; here are the linear head's own loops.
 #include "common.h"
 #include "head_rules.h"
 #include "medp_hip.h"
 
 namespace {
 
-constexpr float kNaNf = __builtin_nanf("");
 constexpr int HT_THREADS = 512, HT_WAVES = HT_THREADS / 64;
 constexpr int HS_THREADS = 256, HS_WAVES = HS_THREADS / 64, HS_ROWS = 32;   // scores: rows per workgroup
 
@@ -66,17 +67,12 @@ __device__ __forceinline__ void head_epoch(const MedpHeadProblem& pb, float* gs,
     const float p = pb.dropout_p, inv_keep = 1.f / (1.f - p);
     const bool drop = p > 0.f;
     const int t0 = pb.t[0];
-    double b1t = pow(pb.beta1, (double)t0), b2t = pow(pb.beta2, (double)t0);
     AdamScalars a;
-    adam_fixed_scalars(a, pb.lr, pb.weight_decay, pb.beta1, pb.beta2, pb.eps);
+    HeadSchedule sched(a, pb.lr, pb.weight_decay, pb.beta1, pb.beta2, pb.eps, pb.seed, t0);
     double run_l = 0.0, run_v = 0.0;
     for (int s = 0; s < pb.S; ++s) {
-        const int t = t0 + s + 1;
-        const uint32_t seed = pb.seed + (uint32_t)t * 0x9E3779B9u;          // medp_mix_epoch with the problem's own step count
+        const uint32_t seed = sched.advance(a);
         const int* pr = pb.perm + (size_t)s * bs;
-        b1t *= pb.beta1;
-        b2t *= pb.beta2;
-        adam_step_scalars(a, pb.lr, b1t, b2t);
         // ---- A: logits into gs
         if (w == 0) {
             for (int r = wave; r < bs; r += HT_WAVES) {
@@ -110,17 +106,9 @@ __device__ __forceinline__ void head_epoch(const MedpHeadProblem& pb, float* gs,
         for (int e = tid; e < bs * L; e += HT_THREADS) {
             const int r = e / L, l = e % L;
             const size_t o = (size_t)pr[r] * pb.ldy + l;
-            const double z = (double)gs[r * LP + l], y = (double)pb.Y[o], m = (double)pb.M[o];
-            const double ex = exp(-fabs(z));
-            part += (fmax(z, 0.0) - y * z + log1p(ex)) * m;
-            const double sg = z >= 0.0 ? 1.0 / (1.0 + ex) : ex / (1.0 + ex);
-            gs[r * LP + l] = vc > 0.0 ? (float)((sg - y) * m / vc) : 0.f;   // vc = 0: the reference's loss is logits.sum() * 0
+            part += masked_bce_term((double)gs[r * LP + l], (double)pb.Y[o], (double)pb.M[o], vc, gs + r * LP + l);
         }
-        const double lsum = block_sum_wave_order_f64<HT_WAVES>(part, red);   // publishes g
-        if (vc > 0.0) {
-            run_l += lsum / vc * vc;
-            run_v += vc;
-        }
+        add_step_loss(run_l, run_v, block_sum_wave_order_f64<HT_WAVES>(part, red), vc);      // the sum's barriers publish g
         // ---- B: gradient of every column in row order, AdamW
         for (int j = tid; j < F; j += HT_THREADS) {
             if (w == 0) {
@@ -185,19 +173,12 @@ __global__ __launch_bounds__(HT_THREADS) void head_train_epoch_kernel(const Medp
         return;
     }
     float* gs = (float*)head_smem;
-    const int lp = head_lp(pb.L);
-    float* st = gs + pb.bs * lp;
     const bool on = head_onchip(pb.F, pb.L, pb.label_width, pb.bs);          // uniform over the workgroup
-    if (lp == 2) {
-        if (on) head_epoch<2, true>(pb, gs, st, red);
-        else head_epoch<2, false>(pb, gs, st, red);
-    } else if (lp == 8) {
-        if (on) head_epoch<8, true>(pb, gs, st, red);
-        else head_epoch<8, false>(pb, gs, st, red);
-    } else {
-        if (on) head_epoch<16, true>(pb, gs, st, red);
-        else head_epoch<16, false>(pb, gs, st, red);
-    }
+    with_head_lp(pb.L, [&](auto lp) {
+        float* st = gs + pb.bs * lp;
+        if (on) head_epoch<lp, true>(pb, gs, st, red);
+        else head_epoch<lp, false>(pb, gs, st, red);
+    });
 }
 
 // grid (ceil(n / HS_ROWS)); wave per row
@@ -223,11 +204,7 @@ __device__ __forceinline__ void head_scores_rows(const float* __restrict__ X, lo
                 for (int k = 0; k < w; ++k) z = fma((double)xr[lane * w + k], (double)W[lane * w + k], z);
             }
         }
-        if (lane < L) {
-            const float zf = ok ? (float)(z + (double)b[lane]) : kNaNf;
-            logits[(size_t)i * L + lane] = zf;
-            probs[(size_t)lane * n + i] = (double)(1.0f / (1.0f + expf(-zf)));
-        }
+        if (lane < L) head_store_score(logits, probs, i, lane, L, n, ok, (float)(z + (double)b[lane]));
     }
 }
 
@@ -235,19 +212,14 @@ __global__ __launch_bounds__(HS_THREADS) void head_scores_kernel(const float* __
                                                                   int w, const float* __restrict__ W, const float* __restrict__ b,
                                                                   const int* __restrict__ rows, int n, float* __restrict__ logits,
                                                                   double* __restrict__ probs) {
-    const int lp = head_lp(L);
-    if (lp == 2) head_scores_rows<2>(X, ldx, N, col0, F, L, w, W, b, rows, n, logits, probs);
-    else if (lp == 8) head_scores_rows<8>(X, ldx, N, col0, F, L, w, W, b, rows, n, logits, probs);
-    else head_scores_rows<16>(X, ldx, N, col0, F, L, w, W, b, rows, n, logits, probs);
+    with_head_lp(L, [&](auto lp) { head_scores_rows<lp>(X, ldx, N, col0, F, L, w, W, b, rows, n, logits, probs); });
 }
 
 int check_head_shape(const char* what, int p, long long ldx, int N, int ldy, int col0, int F, int L, int w) {
     MEDP_CHECK_ARG(F >= 1 && F <= MEDP_HEAD_MAX_F, "%s: problem %d has F=%d, not in [1, %d]", what, p, F, MEDP_HEAD_MAX_F);
-    MEDP_CHECK_ARG(L >= 1 && L <= MEDP_HEAD_MAX_L, "%s: problem %d has L=%d, not in [1, %d]", what, p, L, MEDP_HEAD_MAX_L);
+    MEDP_TRY(check_labels_and_columns(what, p, ldx, N, col0, F, L));
     MEDP_CHECK_ARG(w >= 0 && (w == 0 || (long long)L * w == F), "%s: problem %d has label_width=%d with L=%d, F=%d (F = L label_width is needed)",
                    what, p, w, L, F);
-    MEDP_CHECK_ARG(N >= 1 && col0 >= 0 && (long long)col0 + F <= ldx, "%s: problem %d columns [%d, %lld) leave a row of %lld (N=%d)", what, p,
-                   col0, (long long)col0 + F, ldx, N);
     MEDP_CHECK_ARG(ldy < 0 || ldy >= L, "%s: problem %d has ldy=%d < L=%d", what, p, ldy, L);
     return 0;
 }
@@ -268,14 +240,7 @@ extern "C" int medp_head_train_epoch(const MedpHeadProblem* table_host, const Me
         MEDP_CHECK_ARG(q.X && q.Y && q.M && q.W && q.b && q.mW && q.vW && q.mb && q.vb && q.t && q.perm && q.loss_out,
                        "head_train_epoch: problem %d has a null pointer", p);
         MEDP_TRY(check_head_shape("head_train_epoch", p, q.ldx, q.N, q.ldy, q.col0, q.F, q.L, q.label_width));
-        MEDP_CHECK_ARG(q.bs >= 1 && q.bs <= MEDP_HEAD_MAX_BS, "head_train_epoch: problem %d has bs=%d, not in [1, %d]", p, q.bs,
-                       MEDP_HEAD_MAX_BS);
-        MEDP_CHECK_ARG(q.S >= 1 && (long long)q.S * q.bs <= q.N, "head_train_epoch: problem %d has S=%d steps of %d rows with N=%d", p, q.S,
-                       q.bs, q.N);
-        MEDP_CHECK_ARG(q.dropout_p >= 0.f && q.dropout_p < 1.f, "head_train_epoch: problem %d has dropout_p=%g, not in [0, 1)", p,
-                       (double)q.dropout_p);
-        MEDP_CHECK_ARG(q.lr >= 0.0 && q.beta1 >= 0.0 && q.beta1 < 1.0 && q.beta2 >= 0.0 && q.beta2 < 1.0 && q.eps >= 0.0,
-                       "head_train_epoch: problem %d has bad AdamW scalars", p);
+        MEDP_TRY(check_steps("head_train_epoch", p, q.N, q.bs, q.S, q.dropout_p, q.lr, q.beta1, q.beta2, q.eps));
         long long need = head_g_bytes(q.L, q.bs);
         if (head_onchip(q.F, q.L, q.label_width, q.bs)) need += 12 * head_nw(q.F, q.L, q.label_width);
         lds = need > lds ? need : lds;

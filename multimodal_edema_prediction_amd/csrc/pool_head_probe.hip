@@ -16,14 +16,15 @@
 //   A  thread per (row, hidden unit): pre-activation, exact GELU, dropout     C1  thread per (row, hidden unit): d pre-activation
 //   B  thread per (row, label): logits; vc, g, the loss                       C2  thread per parameter: its gradient over the rows
 //                                                                                 in order, AdamW
-// fp32 in storage; fp64 accumulators; no floating-point atomics; every reduction in a fixed order.
+// fp32 in storage; fp64 accumulators; no floating-point atomics; every reduction in a fixed order.  The rules shared with
+// head_probe.hip are head_rules.h: the pool head's host loop and mlp_epoch step the same HeadSchedule as head_epoch, and the two
+// launchers check their steps, permutations and columns with the same functions.
 #include "common.h"
 #include "head_rules.h"
 #include "medp_hip.h"
 
 namespace {
 
-constexpr float kNaNf = __builtin_nanf("");
 constexpr int PH_THREADS = 512, PH_WAVES = PH_THREADS / 64;
 constexpr int PC_THREADS = 256;                                              // column kernel
 constexpr int MS_THREADS = 256;                                              // mlp scores: thread per row
@@ -233,10 +234,7 @@ __global__ __launch_bounds__(PC_THREADS) void pool_col_kernel(MedpPoolHeadProble
             for (int r = 0; r < bs; ++r) ls += ws.lossp[r];
             const double vc = ws.vc[0];
             double run_l = first ? 0.0 : pb.loss_out[0], run_v = first ? 0.0 : pb.loss_out[1];
-            if (vc > 0.0) {
-                run_l += ls / vc * vc;
-                run_v += vc;
-            }
+            add_step_loss(run_l, run_v, ls, vc);
             pb.loss_out[0] = run_l;
             pb.loss_out[1] = run_v;
         }
@@ -258,11 +256,7 @@ __global__ __launch_bounds__(PH_THREADS) void pool_scores_kernel(const float* __
         float* xs = (float*)(wv + 2 * T);
         pool_forward<LP, ONCHIP>(X + (size_t)row * T * d, xs, wv, sh, q, W, b, T, d, L, false, 0u, 0u, 0u, 0.f, 1.f, nullptr);
     }
-    if (tid < L) {
-        const float zf = ok ? sh.zs[tid] : kNaNf;
-        logits[(size_t)i * L + tid] = zf;
-        probs[(size_t)tid * n + i] = (double)(1.0f / (1.0f + expf(-zf)));
-    }
+    if (tid < L) head_store_score(logits, probs, i, tid, L, n, ok, sh.zs[tid]);
 }
 
 size_t pool_lds_bytes(int T, int d) { return (size_t)(pool_small_bytes(T) + (pool_onchip(T, d) ? 4LL * T * d : 0)); }
@@ -304,22 +298,6 @@ int check_pool_shape(const char* what, int N, int T, int d, int L) {
     return 0;
 }
 
-int check_steps(const char* what, int p, int N, int bs, int S, float dropout_p, double lr, double beta1, double beta2, double eps) {
-    MEDP_CHECK_ARG(bs >= 1 && bs <= MEDP_HEAD_MAX_BS, "%s: problem %d has bs=%d, not in [1, %d]", what, p, bs, MEDP_HEAD_MAX_BS);
-    MEDP_CHECK_ARG(S >= 1 && (long long)S * bs <= N, "%s: problem %d has S=%d steps of %d rows with N=%d", what, p, S, bs, N);
-    MEDP_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "%s: problem %d has dropout_p=%g, not in [0, 1)", what, p, (double)dropout_p);
-    MEDP_CHECK_ARG(lr >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0,
-                   "%s: problem %d has bad AdamW scalars", what, p);
-    return 0;
-}
-
-int check_perm(const char* what, int p, const int* perm_host, long long count, int N) {
-    for (long long i = 0; i < count; ++i)
-        MEDP_CHECK_ARG((unsigned)perm_host[i] < (unsigned)N, "%s: problem %d has permutation entry %lld = %d outside [0, %d)", what, p, i,
-                       perm_host[i], N);
-    return 0;
-}
-
 // ---- MLP fusion head ------------------------------------------------------------------------------------------------------------
 __host__ __device__ inline long long mlp_np(int K, int L, int H) { return (long long)H * K + H + (long long)L * H + L; }
 __host__ __device__ inline long long mlp_lds_bytes(int K, int L, int H, int bs) {
@@ -357,17 +335,12 @@ __device__ __forceinline__ void mlp_epoch(const MedpMlpHeadProblem& pb, float* s
     const float p = pb.dropout_p, inv_keep = 1.f / (1.f - p);
     const bool drop = p > 0.f;
     const int t0 = pb.t[0];
-    double b1t = pow(pb.beta1, (double)t0), b2t = pow(pb.beta2, (double)t0);
     AdamScalars a;
-    adam_fixed_scalars(a, pb.lr, pb.weight_decay, pb.beta1, pb.beta2, pb.eps);
+    HeadSchedule sched(a, pb.lr, pb.weight_decay, pb.beta1, pb.beta2, pb.eps, pb.seed, t0);
     double run_l = 0.0, run_v = 0.0;
     for (int s = 0; s < pb.S; ++s) {
-        const int t = t0 + s + 1;
-        const uint32_t seed = pb.seed + (uint32_t)t * 0x9E3779B9u;          // medp_mix_epoch with the problem's own step count
+        const uint32_t seed = sched.advance(a);
         const int* pr = pb.perm + (size_t)s * bs;
-        b1t *= pb.beta1;
-        b2t *= pb.beta2;
-        adam_step_scalars(a, pb.lr, b1t, b2t);
         // ---- A: pre-activations and the masked hidden activations
         for (int e = tid; e < bs * H; e += PH_THREADS) {
             const int r = e / H, k = e % H;
@@ -397,11 +370,7 @@ __device__ __forceinline__ void mlp_epoch(const MedpMlpHeadProblem& pb, float* s
             const size_t o = (size_t)pr[r] * pb.ldy + l;
             part += masked_bce_term((double)gs[r * LP + l], (double)pb.Y[o], (double)pb.M[o], vc, gs + r * LP + l);
         }
-        const double lsum = block_sum_wave_order_f64<PH_WAVES>(part, red);  // publishes g
-        if (vc > 0.0) {
-            run_l += lsum / vc * vc;
-            run_v += vc;
-        }
+        add_step_loss(run_l, run_v, block_sum_wave_order_f64<PH_WAVES>(part, red), vc);       // the sum's barriers publish g
         // ---- C1: d pre-activation = mask (g W2) gelu'(pre), in place of the pre-activation
         for (int e = tid; e < bs * H; e += PH_THREADS) {
             const int r = e / H, k = e % H;
@@ -451,10 +420,7 @@ __global__ __launch_bounds__(PH_THREADS) void mlp_head_train_epoch_kernel(const 
     extern __shared__ __attribute__((aligned(16))) unsigned char mlp_smem[];
     __shared__ double red[PH_WAVES];
     const MedpMlpHeadProblem pb = tab[blockIdx.x];
-    const int lp = head_lp(pb.L);
-    if (lp == 2) mlp_epoch<2>(pb, (float*)mlp_smem, red);
-    else if (lp == 8) mlp_epoch<8>(pb, (float*)mlp_smem, red);
-    else mlp_epoch<16>(pb, (float*)mlp_smem, red);
+    with_head_lp(pb.L, [&](auto lp) { mlp_epoch<lp>(pb, (float*)mlp_smem, red); });
 }
 
 // thread per scored row
@@ -483,11 +449,7 @@ __device__ __forceinline__ void mlp_scores_row(const float* __restrict__ X, long
     }
 #pragma unroll
     for (int l = 0; l < LP; ++l)
-        if (l < L) {
-            const float zf = ok ? (float)(acc[l] + (double)b2[l]) : kNaNf;
-            logits[(size_t)i * L + l] = zf;
-            probs[(size_t)l * n + i] = (double)(1.0f / (1.0f + expf(-zf)));
-        }
+        if (l < L) head_store_score(logits, probs, i, l, L, n, ok, (float)(acc[l] + (double)b2[l]));
 }
 
 __global__ __launch_bounds__(MS_THREADS) void mlp_head_scores_kernel(const float* __restrict__ X, long long ldx, int N, int col0, int K, int H,
@@ -495,19 +457,13 @@ __global__ __launch_bounds__(MS_THREADS) void mlp_head_scores_kernel(const float
                                                                       const float* __restrict__ W2, const float* __restrict__ b2,
                                                                       const int* __restrict__ rows, int n, float* __restrict__ logits,
                                                                       double* __restrict__ probs) {
-    const int lp = head_lp(L);
-    if (lp == 2) mlp_scores_row<2>(X, ldx, N, col0, K, H, L, W1, b1, W2, b2, rows, n, logits, probs);
-    else if (lp == 8) mlp_scores_row<8>(X, ldx, N, col0, K, H, L, W1, b1, W2, b2, rows, n, logits, probs);
-    else mlp_scores_row<16>(X, ldx, N, col0, K, H, L, W1, b1, W2, b2, rows, n, logits, probs);
+    with_head_lp(L, [&](auto lp) { mlp_scores_row<lp>(X, ldx, N, col0, K, H, L, W1, b1, W2, b2, rows, n, logits, probs); });
 }
 
 int check_mlp_shape(const char* what, int p, long long ldx, int N, int col0, int K, int H, int L) {
     MEDP_CHECK_ARG(K >= 1 && K <= MEDP_MLP_HEAD_MAX_K, "%s: problem %d has K=%d, not in [1, %d]", what, p, K, MEDP_MLP_HEAD_MAX_K);
     MEDP_CHECK_ARG(H >= 1 && H <= MEDP_MLP_HEAD_MAX_H, "%s: problem %d has H=%d, not in [1, %d]", what, p, H, MEDP_MLP_HEAD_MAX_H);
-    MEDP_CHECK_ARG(L >= 1 && L <= MEDP_HEAD_MAX_L, "%s: problem %d has L=%d, not in [1, %d]", what, p, L, MEDP_HEAD_MAX_L);
-    MEDP_CHECK_ARG(N >= 1 && col0 >= 0 && (long long)col0 + K <= ldx, "%s: problem %d columns [%d, %lld) leave a row of %lld (N=%d)", what, p,
-                   col0, (long long)col0 + K, ldx, N);
-    return 0;
+    return check_labels_and_columns(what, p, ldx, N, col0, K, L);
 }
 
 }  // namespace
@@ -537,19 +493,11 @@ extern "C" int medp_pool_head_train_epoch(const MedpPoolHeadProblem* pbp, const 
     MEDP_TRY(check_perm(what, 0, perm_host, (long long)pb.S * pb.bs, pb.N));
     MEDP_CHECK_ARG(pb.perm, "%s: null device permutation", what);           // after the checks: they can be driven without a device
     AdamScalars a;
-    adam_fixed_scalars(a, pb.lr, pb.weight_decay, pb.beta1, pb.beta2, pb.eps);
-    double b1t = pow(pb.beta1, (double)pb.step0), b2t = pow(pb.beta2, (double)pb.step0);
-    const int lp = head_lp(pb.L);
+    HeadSchedule sched(a, pb.lr, pb.weight_decay, pb.beta1, pb.beta2, pb.eps, pb.seed, pb.step0);
     for (int s = 0; s < pb.S; ++s) {
-        const int t = pb.step0 + s + 1;
-        const uint32_t seed = pb.seed + (uint32_t)t * 0x9E3779B9u;          // as head_epoch mixes its step number
-        b1t *= pb.beta1;
-        b2t *= pb.beta2;
-        adam_step_scalars(a, pb.lr, b1t, b2t);
+        const uint32_t seed = sched.advance(a);
         const int* perm = pb.perm + (size_t)s * pb.bs;
-        if (lp == 2) MEDP_TRY(launch_pool_step<2>(pb, perm, seed, a, s == 0, (hipStream_t)stream));
-        else if (lp == 8) MEDP_TRY(launch_pool_step<8>(pb, perm, seed, a, s == 0, (hipStream_t)stream));
-        else MEDP_TRY(launch_pool_step<16>(pb, perm, seed, a, s == 0, (hipStream_t)stream));
+        MEDP_TRY(with_head_lp(pb.L, [&](auto lp) { return launch_pool_step<lp>(pb, perm, seed, a, s == 0, (hipStream_t)stream); }));
     }
     return 0;
 }
@@ -559,16 +507,11 @@ extern "C" int medp_pool_head_scores(const float* X, int N, int T, int d, int L,
     MEDP_TRY(check_pool_shape("pool_head_scores", N, T, d, L));
     MEDP_CHECK_ARG(n >= 1, "pool_head_scores: n=%d < 1", n);
     MEDP_CHECK_ARG(X && q && W && b && logits && probs, "pool_head_scores: null argument");
-    const int lp = head_lp(L);
-    const bool on = pool_onchip(T, d);
     hipStream_t st = (hipStream_t)stream;
-#define MEDP_POOL_SCORES(LP)                                                                                        \
-    return on ? launch_pool_scores<LP, true>(X, N, T, d, L, q, W, b, rows, n, logits, probs, st)                     \
-              : launch_pool_scores<LP, false>(X, N, T, d, L, q, W, b, rows, n, logits, probs, st)
-    if (lp == 2) MEDP_POOL_SCORES(2);
-    if (lp == 8) MEDP_POOL_SCORES(8);
-    MEDP_POOL_SCORES(16);
-#undef MEDP_POOL_SCORES
+    return with_head_lp(L, [&](auto lp) {
+        return pool_onchip(T, d) ? launch_pool_scores<lp, true>(X, N, T, d, L, q, W, b, rows, n, logits, probs, st)
+                                 : launch_pool_scores<lp, false>(X, N, T, d, L, q, W, b, rows, n, logits, probs, st);
+    });
 }
 
 extern "C" int medp_mlp_head_supported(int K, int L, int H, int bs) {

@@ -18,7 +18,9 @@ The two heads with a hidden stage run on csrc/pool_head_probe.hip:
                 of an epoch from one call.  Python counts the steps (the kernels keep no device counter).
   MLP fusion    `MlpHeadProblem`, `train_mlp_heads`: every step of an epoch in one launch, a workgroup per problem, parameters,
                 moments and activations in LDS.
-All three trainers share one selection rule (`BestSelection`).  `eager_fit` is the reference's loop through torch autograd: the
+The three problem classes share one base (`_Problem`: labels, minibatch grid, AdamW and dropout fields), the three scores wrappers
+one buffer helper, and the three trainers one epoch loop (`_train`) and one selection rule (`BestSelection`): a trainer says how its
+family launches an epoch and scores a problem, nothing else.  `eager_fit` is the reference's loop through torch autograd: the
 fallback for a shape outside the kernels' limits, and the baseline the timing tool compares with.  Without a GPU every entry point
 raises (no CPU fallback)."""
 from __future__ import annotations
@@ -62,33 +64,45 @@ def onchip(F: int, L: int, label_width: int, bs: int) -> bool:
     return bool(lib().medp_head_train_onchip(int(F), int(L), int(label_width), int(bs)))
 
 
-class HeadProblem:
+class _Problem:
+    """What the three problems share, once `X` and `N` are set: the labels Y / M [N, >= L], the minibatch grid (bs, S), AdamW's
+    hyper-parameters, the dropout stream, and `own`, the device copy of an initial parameter."""
+
+    def __init__(self, Y, M, bs, lr, weight_decay, dropout, seed, stream_id, betas, eps):
+        self.Y, ny, self.ldy = fp32_matrix(Y, "Y")
+        self.M, nm, ldm = fp32_matrix(M, "M")
+        if ny != self.N or nm != self.N or ldm != self.ldy:
+            raise ValueError(f"{type(self).__name__}: X has {self.N} rows, Y {ny} x {self.ldy}, M {nm} x {ldm}")
+        self.bs, self.S = int(bs), self.N // max(int(bs), 1)
+        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
+        self.dropout, self.seed, self.stream_id = float(dropout), int(seed) & 0xFFFFFFFF, int(stream_id) & 0xFFFFFFFF
+
+    def own(self, t: torch.Tensor) -> torch.Tensor:
+        return t.detach().to(device=self.X.device, dtype=torch.float32).contiguous().clone()
+
+
+class HeadProblem(_Problem):
     """One head: z = (x o dropout) W^T + b over the columns [col0, col0 + F) of X.  `label_width` = 0: W [L, F]; w > 0: label l reads
     columns [l w, (l+1) w) and W is [L, w].  Parameters, Adam moments and the step count live on the device."""
 
     def __init__(self, X, Y, M, W, b, *, col0: int = 0, F: int | None = None, label_width: int = 0, bs: int = 128, lr: float = 1e-4,
                  weight_decay: float = 1e-4, dropout: float = 0.0, seed: int = 0, stream_id: int = 0, betas=BETAS, eps: float = EPS):
         self.X, self.N, self.ldx = fp32_matrix(X, "X")
-        self.Y, ny, self.ldy = fp32_matrix(Y, "Y")
-        self.M, nm, ldm = fp32_matrix(M, "M")
-        if ny != self.N or nm != self.N or ldm != self.ldy:
-            raise ValueError(f"HeadProblem: X has {self.N} rows, Y {ny} x {self.ldy}, M {nm} x {ldm}")
-        dev = self.X.device
-        self.W = W.detach().to(device=dev, dtype=torch.float32).contiguous().clone()
-        self.b = b.detach().to(device=dev, dtype=torch.float32).contiguous().clone()
+        super().__init__(Y, M, bs, lr, weight_decay, dropout, seed, stream_id, betas, eps)
+        self.W, self.b = self.own(W), self.own(b)
         self.L = int(self.b.numel())
         self.label_width = int(label_width)
         self.col0 = int(col0)
         self.F = int(F) if F is not None else (self.ldx - self.col0)
         self.mW, self.vW = torch.zeros_like(self.W), torch.zeros_like(self.W)
         self.mb, self.vb = torch.zeros_like(self.b), torch.zeros_like(self.b)
-        self.t = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.bs, self.S = int(bs), self.N // max(int(bs), 1)
-        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
-        self.dropout, self.seed, self.stream_id = float(dropout), int(seed) & 0xFFFFFFFF, int(stream_id) & 0xFFFFFFFF
+        self.t = torch.zeros(1, dtype=torch.int32, device=self.X.device)
         expect = self.L * (self.label_width if self.label_width > 0 else self.F)
         if self.W.numel() != expect:
             raise ValueError(f"HeadProblem: W has {self.W.numel()} elements, L={self.L}, F={self.F}, label_width={self.label_width} need {expect}")
+
+    def live(self) -> dict:
+        return {"best_W": self.W, "best_b": self.b}
 
     def entry(self, perm: torch.Tensor | None, loss_out: torch.Tensor | None) -> MedpHeadProblem:
         return MedpHeadProblem(ptr(self.X), ptr(self.Y), ptr(self.M), ptr(self.W), ptr(self.b), ptr(self.mW), ptr(self.vW), ptr(self.mb),
@@ -97,10 +111,26 @@ class HeadProblem:
                                self.dropout, self.seed, self.stream_id, 0)
 
 
+def _table(struct, entries: Sequence):
+    host = (struct * max(len(entries), 1))(*entries)
+    return host, table_bytes(host, len(entries))
+
+
 def make_table(entries: Sequence[MedpHeadProblem]):
     """(host ctypes array, the same bytes as a uint8 numpy array)."""
-    host = (MedpHeadProblem * max(len(entries), 1))(*entries)
-    return host, table_bytes(host, len(entries))
+    return _table(MedpHeadProblem, entries)
+
+
+def make_mlp_table(entries: Sequence[MedpMlpHeadProblem]):
+    """(host ctypes array, the same bytes as a uint8 numpy array)."""
+    return _table(MedpMlpHeadProblem, entries)
+
+
+def _table_launcher(struct, train_epoch, what: str, entries: Sequence[Sequence], dev) -> Callable:
+    """Every epoch's problem table (entries[e]) built and uploaded in one copy; returns launch(e)."""
+    tables = [_table(struct, en) for en in entries]
+    tables_dev = torch.as_tensor(np.stack([t[1] for t in tables]) if tables else np.zeros((0, 1), np.uint8), device=dev)
+    return lambda e: check(train_epoch(tables[e][0], ptr(tables_dev[e]), len(entries[e]), stream()), what)
 
 
 def check_table(entries: Sequence[MedpHeadProblem]) -> None:
@@ -120,10 +150,20 @@ def head_train_epoch(problems: Sequence[HeadProblem], perms: Sequence[torch.Tens
     for pb, perm in zip(problems, perms):
         if perm.dtype != torch.int32 or perm.numel() < pb.S * pb.bs or not perm.is_contiguous():
             raise ValueError("head_train_epoch: a permutation is a contiguous int32 tensor of at least S * bs entries")
-    host, raw = make_table([pb.entry(perm, loss_out[p]) for p, (pb, perm) in enumerate(zip(problems, perms))])
-    table_dev = torch.as_tensor(raw, device=dev)
-    check(lib().medp_head_train_epoch(host, ptr(table_dev), len(problems), stream()), "head_train_epoch")
+    entries = [pb.entry(perm, loss_out[p]) for p, (pb, perm) in enumerate(zip(problems, perms))]
+    _table_launcher(MedpHeadProblem, lib().medp_head_train_epoch, "head_train_epoch", [entries], dev)(0)
     return loss_out
+
+
+def _score_buffers(who: str, X: torch.Tensor, L: int, rows, logits, probs):
+    """(n, logits [n, L] fp32, probs [L, n] fp64) of a scores call over the rows `rows` of X (int32; None: all n = N rows); the two
+    buffers are allocated unless given."""
+    if rows is not None and rows.dtype != torch.int32:
+        raise TypeError(f"{who}: rows are int32")
+    n = X.shape[0] if rows is None else int(rows.numel())
+    logits = torch.empty((n, L), dtype=torch.float32, device=X.device) if logits is None else logits
+    probs = torch.empty((L, n), dtype=torch.float64, device=X.device) if probs is None else probs
+    return n, logits, probs
 
 
 def head_scores(X, W, b, *, col0: int = 0, F: int | None = None, label_width: int = 0, rows: torch.Tensor | None = None, logits=None,
@@ -133,13 +173,9 @@ def head_scores(X, W, b, *, col0: int = 0, F: int | None = None, label_width: in
     X, N, ldx = fp32_matrix(X, "X")
     L = int(b.numel())
     F = ldx - col0 if F is None else F
-    n = N if rows is None else int(rows.numel())
-    if rows is not None and rows.dtype != torch.int32:
-        raise TypeError("head_scores: rows are int32")
+    n, logits, probs = _score_buffers("head_scores", X, L, rows, logits, probs)
     if W.dtype != torch.float32 or b.dtype != torch.float32 or W.numel() != L * (label_width if label_width > 0 else F):
         raise ValueError("head_scores: W fp32 [L, F] (or [L, label_width]), b fp32 [L]")
-    logits = torch.empty((n, L), dtype=torch.float32, device=X.device) if logits is None else logits
-    probs = torch.empty((L, n), dtype=torch.float64, device=X.device) if probs is None else probs
     check(lib().medp_head_scores(ptr(X), ldx, N, int(col0), int(F), L, int(label_width), ptr(W.contiguous()), ptr(b.contiguous()), ptr(rows),
                                  n, ptr(logits), ptr(probs), stream()), "head_scores")
     return logits, probs
@@ -190,49 +226,66 @@ class BestSelection:
         return res
 
 
+def _epoch_perms(perms, E: int, count: int, who: str) -> np.ndarray:
+    host = np.ascontiguousarray(np.asarray(perms)[:, :count], dtype=np.int32)
+    if host.shape != (E, count):
+        raise ValueError(f"{who}: [{E}, {count}] permutation entries are needed, got {tuple(host.shape)}")
+    return host
+
+
+def _train(who: str, problems: Sequence, vals: Sequence[tuple], epochs: int, perms: Sequence, record_val_logits: bool, prepare: Callable,
+           score: Callable, entry: Callable = lambda pb, perm_dev, perm_host, loss_out: pb.entry(perm_dev, loss_out),
+           check_losses: Callable = lambda p, pb, losses_h: None) -> list:
+    """The epoch loop of the three trainers.  The order fixes what is raised before the first launch: the metrics, the row orders
+    (one upload per problem), every epoch's entries (`entry`), then `prepare(entries [E][P], hosts, dev)`, which uploads what the
+    family keeps on the device and returns launch(e).  The loop copies nothing to or from the device: per epoch launch(e), then
+    `score(pb, X_va, logits=, probs=)` and the selection of every problem; one synchronise and one copy of the losses at the end."""
+    require_gpu()
+    P, E = len(problems), int(epochs)
+    dev = problems[0].X.device
+    metrics = [LabelMetrics(v[1].to(dev), v[2].to(dev)) for v in vals]                 # raises before the first launch
+    Xv = [fp32_matrix(v[0].to(dev), "X_va")[0] for v in vals]
+    hosts = [_epoch_perms(pm, E, pb.S * pb.bs, who) for pb, pm in zip(problems, perms)]
+    perm_dev = [torch.as_tensor(h, device=dev) for h in hosts]
+    losses = torch.zeros((E, P, 2), dtype=torch.float64, device=dev)
+    launch = prepare([[entry(pb, perm_dev[p][e], hosts[p][e], losses[e, p]) for p, pb in enumerate(problems)] for e in range(E)], hosts, dev)
+    sel = [BestSelection(E, pb.live(), metrics[p], Xv[p].shape[0], pb.L, record_val_logits) for p, pb in enumerate(problems)]
+    for e in range(E):
+        launch(e)
+        for p, pb in enumerate(problems):
+            logits, probs = sel[p].buffers(e)
+            score(pb, Xv[p], logits=logits, probs=probs)
+            sel[p].update(e)
+    torch.cuda.synchronize(dev)
+    losses_h = losses.cpu().numpy()
+    out = []
+    for p, pb in enumerate(problems):
+        check_losses(p, pb, losses_h[:, p])
+        out.append(sel[p].result(losses_h[:, p]))
+    return out
+
+
 def train_heads(problems: Sequence[HeadProblem], vals: Sequence[tuple], epochs: int, perms: Sequence[np.ndarray],
                 record_val_logits: bool = False) -> list:
     """`epochs` epochs of every problem, one launch group per epoch, best-validation-macro-AUROC selection on the device.
     vals[p] = (X_va, Y_va, M_va) with the problem's column layout; perms[p]: [epochs, >= S bs] int host array.
     One result dict per problem: curve [E], loss_sum / valid_sum [E], best_epoch (1-based), best_val, best_W / best_b, and
     val_logits [E, n, L] when asked for.  Raises ValueError when no epoch has a defined macro AUROC, or a permutation was bad."""
-    require_gpu()
-    P, E = len(problems), int(epochs)
-    dev = problems[0].X.device
-    metrics = [LabelMetrics(v[1].to(dev), v[2].to(dev)) for v in vals]                 # raises before the first launch
-    Xv = [fp32_matrix(v[0].to(dev), "X_va")[0] for v in vals]
-    perm_dev = [torch.as_tensor(np.ascontiguousarray(np.asarray(pm)[:, :pb.S * pb.bs], dtype=np.int32), device=dev)
-                for pb, pm in zip(problems, perms)]
-    for pb, pd in zip(problems, perm_dev):
-        if pd.shape != (E, pb.S * pb.bs):
-            raise ValueError(f"train_heads: a problem needs [{E}, {pb.S * pb.bs}] permutation entries, got {tuple(pd.shape)}")
-    losses = torch.zeros((E, P, 2), dtype=torch.float64, device=dev)
-    # every epoch's table up front: the loop copies nothing to or from the device
-    tables = [make_table([pb.entry(perm_dev[p][e], losses[e, p]) for p, pb in enumerate(problems)]) for e in range(E)]
-    host0 = tables[0][0] if E else None
-    if E:
-        rc = lib().medp_head_train_epoch(host0, None, P, None)                         # validate; a null device table is never launched
-        if rc != 0 and b"null device table" not in lib().medp_last_error():
-            check(rc, "head_train_epoch")
-    tables_dev = torch.as_tensor(np.stack([t[1] for t in tables]) if E else np.zeros((0, 1), np.uint8), device=dev)
-    sel = []
-    for p, pb in enumerate(problems):
-        n = Xv[p].shape[0]
-        sel.append(BestSelection(E, {"best_W": pb.W, "best_b": pb.b}, metrics[p], n, pb.L, record_val_logits))
-    for e in range(E):
-        check(lib().medp_head_train_epoch(tables[e][0], ptr(tables_dev[e]), P, stream()), "head_train_epoch")
-        for p, pb in enumerate(problems):
-            logits, probs = sel[p].buffers(e)
-            head_scores(Xv[p], pb.W, pb.b, col0=pb.col0, F=pb.F, label_width=pb.label_width, logits=logits, probs=probs)
-            sel[p].update(e)
-    torch.cuda.synchronize(dev)
-    losses_h = losses.cpu().numpy()
-    out = []
-    for p, pb in enumerate(problems):
-        if np.isnan(losses_h[:, p]).any():
+    def prepare(entries, hosts, dev):
+        if entries:
+            try:
+                check_table(entries[0])                                                # a null device table is never launched
+            except ValueError as err:
+                if "null device table" not in str(err):
+                    raise
+        return _table_launcher(MedpHeadProblem, lib().medp_head_train_epoch, "head_train_epoch", entries, dev)
+
+    def nan_loss(p, pb, losses_h):                                                     # what the kernel leaves of a bad permutation
+        if np.isnan(losses_h).any():
             raise ValueError(f"train_heads: problem {p} has a permutation entry outside [0, {pb.N})")
-        out.append(sel[p].result(losses_h[:, p]))
-    return out
+
+    return _train("train_heads", problems, vals, epochs, perms, record_val_logits, prepare, check_losses=nan_loss,
+                  score=lambda pb, Xv, **out: head_scores(Xv, pb.W, pb.b, col0=pb.col0, F=pb.F, label_width=pb.label_width, **out))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -261,7 +314,7 @@ def _perm_pair(perm, count: int, dev):
     return host, (torch.as_tensor(host, device=dev) if dev is not None else None)
 
 
-class PoolHeadProblem:
+class PoolHeadProblem(_Problem):
     """`LinearHead(use_attn_pool=True)` over X [N, T, d]: attn_query q [d], head.1.weight W [L, d], head.1.bias b [L].  Parameters,
     Adam moments and the workspace live on the device; `steps` (host) counts the steps taken."""
 
@@ -271,22 +324,15 @@ class PoolHeadProblem:
             raise TypeError("PoolHeadProblem: X is fp32 [N, T, d]")
         self.X = X.contiguous()
         self.N, self.T, self.d = (int(v) for v in self.X.shape)
-        self.Y, ny, self.ldy = fp32_matrix(Y, "Y")
-        self.M, nm, ldm = fp32_matrix(M, "M")
-        if ny != self.N or nm != self.N or ldm != self.ldy:
-            raise ValueError(f"PoolHeadProblem: X has {self.N} rows, Y {ny} x {self.ldy}, M {nm} x {ldm}")
-        dev = self.X.device
-        own = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous().clone()  # noqa: E731
-        self.q, self.W, self.b = own(q), own(W), own(b)
+        super().__init__(Y, M, bs, lr, weight_decay, dropout, seed, stream_id, betas, eps)
+        self.q, self.W, self.b = self.own(q), self.own(W), self.own(b)
         self.L = int(self.b.numel())
         if self.q.numel() != self.d or self.W.numel() != self.L * self.d:
             raise ValueError(f"PoolHeadProblem: q has {self.q.numel()} and W {self.W.numel()} elements, d={self.d}, L={self.L}")
         self.mq, self.vq, self.mW, self.vW, self.mb, self.vb = (torch.zeros_like(t) for t in (self.q, self.q, self.W, self.W, self.b, self.b))
-        self.bs, self.S, self.steps = int(bs), self.N // max(int(bs), 1), 0
-        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
-        self.dropout, self.seed, self.stream_id = float(dropout), int(seed) & 0xFFFFFFFF, int(stream_id) & 0xFFFFFFFF
+        self.steps = 0
         nbytes = int(lib().medp_pool_head_ws_bytes(self.d, min(max(self.L, 1), MAX_L), max(self.bs, 1)))
-        self.ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev) if self.X.is_cuda else None
+        self.ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.X.device) if self.X.is_cuda else None
 
     def live(self) -> dict:
         return {"attn_query": self.q, "head.1.weight": self.W, "head.1.bias": self.b}
@@ -321,19 +367,15 @@ def pool_head_scores(X, q, W, b, *, rows: torch.Tensor | None = None, logits=Non
     X = X.contiguous()
     N, T, d = (int(v) for v in X.shape)
     L = int(b.numel())
-    n = N if rows is None else int(rows.numel())
-    if rows is not None and rows.dtype != torch.int32:
-        raise TypeError("pool_head_scores: rows are int32")
+    n, logits, probs = _score_buffers("pool_head_scores", X, L, rows, logits, probs)
     if any(t.dtype != torch.float32 for t in (q, W, b)) or q.numel() != d or W.numel() != L * d:
         raise ValueError("pool_head_scores: q fp32 [d], W fp32 [L, d], b fp32 [L]")
-    logits = torch.empty((n, L), dtype=torch.float32, device=X.device) if logits is None else logits
-    probs = torch.empty((L, n), dtype=torch.float64, device=X.device) if probs is None else probs
     check(lib().medp_pool_head_scores(ptr(X), N, T, d, L, ptr(q.contiguous()), ptr(W.contiguous()), ptr(b.contiguous()), ptr(rows), n,
                                       ptr(logits), ptr(probs), stream()), "pool_head_scores")
     return logits, probs
 
 
-class MlpHeadProblem:
+class MlpHeadProblem(_Problem):
     """`LogitFusionHead("mlp")` over the K columns [col0, col0 + K) of X: head.0.weight W1 [H, K], head.0.bias b1 [H], head.3.weight
     W2 [L, H], head.3.bias b2 [L].  Parameters, Adam moments (one buffer: first then second, in the order W1, b1, W2, b2) and the step
     count live on the device."""
@@ -341,24 +383,16 @@ class MlpHeadProblem:
     def __init__(self, X, Y, M, W1, b1, W2, b2, *, col0: int = 0, K: int | None = None, bs: int = 128, lr: float = 1e-3,
                  weight_decay: float = 1e-4, dropout: float = 0.0, seed: int = 0, stream_id: int = 0, betas=BETAS, eps: float = EPS):
         self.X, self.N, self.ldx = fp32_matrix(X, "X")
-        self.Y, ny, self.ldy = fp32_matrix(Y, "Y")
-        self.M, nm, ldm = fp32_matrix(M, "M")
-        if ny != self.N or nm != self.N or ldm != self.ldy:
-            raise ValueError(f"MlpHeadProblem: X has {self.N} rows, Y {ny} x {self.ldy}, M {nm} x {ldm}")
-        dev = self.X.device
-        own = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous().clone()  # noqa: E731
-        self.W1, self.b1, self.W2, self.b2 = own(W1), own(b1), own(W2), own(b2)
+        super().__init__(Y, M, bs, lr, weight_decay, dropout, seed, stream_id, betas, eps)
+        self.W1, self.b1, self.W2, self.b2 = self.own(W1), self.own(b1), self.own(W2), self.own(b2)
         self.col0 = int(col0)
         self.K = int(K) if K is not None else self.ldx - self.col0
         self.H, self.L = int(self.b1.numel()), int(self.b2.numel())
         if self.W1.numel() != self.H * self.K or self.W2.numel() != self.L * self.H:
             raise ValueError(f"MlpHeadProblem: W1 has {self.W1.numel()} and W2 {self.W2.numel()} elements, K={self.K}, H={self.H}, L={self.L}")
         self.n_params = self.H * self.K + self.H + self.L * self.H + self.L
-        self.mom = torch.zeros(2 * self.n_params, dtype=torch.float32, device=dev)
-        self.t = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.bs, self.S = int(bs), self.N // max(int(bs), 1)
-        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), (float(betas[0]), float(betas[1])), float(eps)
-        self.dropout, self.seed, self.stream_id = float(dropout), int(seed) & 0xFFFFFFFF, int(stream_id) & 0xFFFFFFFF
+        self.mom = torch.zeros(2 * self.n_params, dtype=torch.float32, device=self.X.device)
+        self.t = torch.zeros(1, dtype=torch.int32, device=self.X.device)
 
     def live(self) -> dict:
         return {"head.0.weight": self.W1, "head.0.bias": self.b1, "head.3.weight": self.W2, "head.3.bias": self.b2}
@@ -371,12 +405,6 @@ class MlpHeadProblem:
                                   self.betas[1], self.eps, self.dropout, self.seed, self.stream_id, 0)
 
 
-def make_mlp_table(entries: Sequence[MedpMlpHeadProblem]):
-    """(host ctypes array, the same bytes as a uint8 numpy array)."""
-    host = (MedpMlpHeadProblem * max(len(entries), 1))(*entries)
-    return host, table_bytes(host, len(entries))
-
-
 def mlp_head_train_epoch(problems: Sequence[MlpHeadProblem], perms: Sequence, loss_out: torch.Tensor | None = None) -> torch.Tensor:
     """One epoch of every problem in ONE launch.  perms[p]: at least S bs row indices (host array or tensor).  Returns loss_out [P, 2]."""
     require_gpu()
@@ -384,9 +412,8 @@ def mlp_head_train_epoch(problems: Sequence[MlpHeadProblem], perms: Sequence, lo
     if loss_out is None:
         loss_out = torch.empty((len(problems), 2), dtype=torch.float64, device=dev)
     pairs = [_perm_pair(pm, pb.S * pb.bs, dev) for pb, pm in zip(problems, perms)]
-    host, raw = make_mlp_table([pb.entry(pd, ph, loss_out[p]) for p, (pb, (ph, pd)) in enumerate(zip(problems, pairs))])
-    table_dev = torch.as_tensor(raw, device=dev)
-    check(lib().medp_mlp_head_train_epoch(host, ptr(table_dev), len(problems), stream()), "mlp_head_train_epoch")
+    entries = [pb.entry(pd, ph, loss_out[p]) for p, (pb, (ph, pd)) in enumerate(zip(problems, pairs))]
+    _table_launcher(MedpMlpHeadProblem, lib().medp_mlp_head_train_epoch, "mlp_head_train_epoch", [entries], dev)(0)
     return loss_out
 
 
@@ -396,73 +423,39 @@ def mlp_head_scores(X, W1, b1, W2, b2, *, col0: int = 0, K: int | None = None, r
     X, N, ldx = fp32_matrix(X, "X")
     H, L = int(b1.numel()), int(b2.numel())
     K = ldx - col0 if K is None else K
-    n = N if rows is None else int(rows.numel())
-    if rows is not None and rows.dtype != torch.int32:
-        raise TypeError("mlp_head_scores: rows are int32")
+    n, logits, probs = _score_buffers("mlp_head_scores", X, L, rows, logits, probs)
     if any(t.dtype != torch.float32 for t in (W1, b1, W2, b2)) or W1.numel() != H * K or W2.numel() != L * H:
         raise ValueError("mlp_head_scores: W1 fp32 [H, K], b1 fp32 [H], W2 fp32 [L, H], b2 fp32 [L]")
-    logits = torch.empty((n, L), dtype=torch.float32, device=X.device) if logits is None else logits
-    probs = torch.empty((L, n), dtype=torch.float64, device=X.device) if probs is None else probs
     check(lib().medp_mlp_head_scores(ptr(X), ldx, N, int(col0), int(K), H, L, ptr(W1.contiguous()), ptr(b1.contiguous()), ptr(W2.contiguous()),
                                      ptr(b2.contiguous()), ptr(rows), n, ptr(logits), ptr(probs), stream()), "mlp_head_scores")
     return logits, probs
-
-
-def _epoch_perms(perms, E: int, count: int, who: str) -> np.ndarray:
-    host = np.ascontiguousarray(np.asarray(perms)[:, :count], dtype=np.int32)
-    if host.shape != (E, count):
-        raise ValueError(f"{who}: [{E}, {count}] permutation entries are needed, got {tuple(host.shape)}")
-    return host
 
 
 def train_pool_head(pb: PoolHeadProblem, val: tuple, epochs: int, perms: np.ndarray, record_val_logits: bool = False) -> dict:
     """`train_heads` for the attention-pooled head: per epoch one `medp_pool_head_train_epoch` call and one scores launch, the
     selection of `BestSelection`, one synchronise at the end.  val = (X_va [n, T, d], Y_va, M_va); perms [epochs, >= S bs].
     The result dict of `train_heads` with the best `attn_query`, `head.1.weight`, `head.1.bias` in place of best_W / best_b."""
-    require_gpu()
-    E, dev = int(epochs), pb.X.device
-    metrics = LabelMetrics(val[1].to(dev), val[2].to(dev))                             # raises before the first launch
-    Xv = val[0].to(dev).contiguous()
-    host = _epoch_perms(perms, E, pb.S * pb.bs, "train_pool_head")
-    perm_dev = torch.as_tensor(host, device=dev)                                       # every epoch's row order in one copy
-    losses = torch.zeros((E, 2), dtype=torch.float64, device=dev)
-    sel = BestSelection(E, pb.live(), metrics, Xv.shape[0], pb.L, record_val_logits)
-    for e in range(E):
-        entry = pb.entry(perm_dev[e], losses[e])
-        check(lib().medp_pool_head_train_epoch(ctypes.byref(entry), host[e].ctypes.data, stream()), "pool_head_train_epoch")
-        pb.steps += pb.S
-        logits, probs = sel.buffers(e)
-        pool_head_scores(Xv, pb.q, pb.W, pb.b, logits=logits, probs=probs)
-        sel.update(e)
-    torch.cuda.synchronize(dev)
-    return sel.result(losses.cpu().numpy())
+    def prepare(entries, hosts, dev):
+        for e, (entry,) in enumerate(entries):
+            entry.step0 += e * pb.S                                                    # the kernels keep no counter of their own
+
+        def launch(e):
+            check(lib().medp_pool_head_train_epoch(ctypes.byref(entries[e][0]), hosts[0][e].ctypes.data, stream()), "pool_head_train_epoch")
+            pb.steps += pb.S
+        return launch
+
+    return _train("train_pool_head", [pb], [val], epochs, [perms], record_val_logits, prepare,
+                  score=lambda pb, Xv, **out: pool_head_scores(Xv, pb.q, pb.W, pb.b, **out))[0]
 
 
 def train_mlp_heads(problems: Sequence[MlpHeadProblem], vals: Sequence[tuple], epochs: int, perms: Sequence[np.ndarray],
                     record_val_logits: bool = False) -> list:
     """`train_heads` for MLP fusion heads: one launch per epoch serves every problem.  vals[p] = (X_va, Y_va, M_va) with the problem's
     column layout.  The result dicts carry the best `head.0.weight`, `head.0.bias`, `head.3.weight`, `head.3.bias`."""
-    require_gpu()
-    P, E = len(problems), int(epochs)
-    dev = problems[0].X.device
-    metrics = [LabelMetrics(v[1].to(dev), v[2].to(dev)) for v in vals]                 # raises before the first launch
-    Xv = [fp32_matrix(v[0].to(dev), "X_va")[0] for v in vals]
-    hosts = [_epoch_perms(pm, E, pb.S * pb.bs, "train_mlp_heads") for pb, pm in zip(problems, perms)]
-    perm_dev = [torch.as_tensor(h, device=dev) for h in hosts]
-    losses = torch.zeros((E, P, 2), dtype=torch.float64, device=dev)
-    # every epoch's table up front: the loop copies nothing to or from the device
-    tables = [make_mlp_table([pb.entry(perm_dev[p][e], hosts[p][e], losses[e, p]) for p, pb in enumerate(problems)]) for e in range(E)]
-    tables_dev = torch.as_tensor(np.stack([t[1] for t in tables]) if E else np.zeros((0, 1), np.uint8), device=dev)
-    sel = [BestSelection(E, pb.live(), metrics[p], Xv[p].shape[0], pb.L, record_val_logits) for p, pb in enumerate(problems)]
-    for e in range(E):
-        check(lib().medp_mlp_head_train_epoch(tables[e][0], ptr(tables_dev[e]), P, stream()), "mlp_head_train_epoch")
-        for p, pb in enumerate(problems):
-            logits, probs = sel[p].buffers(e)
-            mlp_head_scores(Xv[p], pb.W1, pb.b1, pb.W2, pb.b2, col0=pb.col0, K=pb.K, logits=logits, probs=probs)
-            sel[p].update(e)
-    torch.cuda.synchronize(dev)
-    losses_h = losses.cpu().numpy()
-    return [sel[p].result(losses_h[:, p]) for p in range(P)]
+    return _train("train_mlp_heads", problems, vals, epochs, perms, record_val_logits,
+                  lambda entries, hosts, dev: _table_launcher(MedpMlpHeadProblem, lib().medp_mlp_head_train_epoch, "mlp_head_train_epoch", entries, dev),
+                  score=lambda pb, Xv, **out: mlp_head_scores(Xv, pb.W1, pb.b1, pb.W2, pb.b2, col0=pb.col0, K=pb.K, **out),
+                  entry=lambda pb, perm_dev, perm_host, loss_out: pb.entry(perm_dev, perm_host, loss_out))
 
 
 def history_lines(result: dict, tag: str = "epoch") -> list:
