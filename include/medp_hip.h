@@ -113,7 +113,8 @@ int medp_attn_bwd_dh64(const void* q, const void* k, const void* v, int ldqkv, c
                        const float* lse, const float* dsum, float* dq, float* dk, float* dv, int ldd, int B, int S, int H,
                        float scale, void* stream);
 /* Small fp32 attention (head dim <= 64, Lk <= 1536), fwd/bwd with optional dropout on the probabilities and
- * optional head-averaged weights (pre-zeroed [B,Lq,Lk]): x_transformers Attention inside the DuETT encoders
+ * optional head-averaged weights ([B,Lq,Lk]; every element is written once, heads added in a fixed order: bitwise
+ * reproducible, need not be zeroed): x_transformers Attention inside the DuETT encoders
  * (model :81,:91) and nn.MultiheadAttention inside _PerceiverBlock (model :759-762, need_weights/average).
  * Few queries over more than 1024 keys: medp_attn_fq_split_* below. */
 int medp_attn_small_fwd(const float* q, int ldq, long long q_batch_stride, const float* k, const float* v, int ldkv,
@@ -515,6 +516,45 @@ int medp_offset_logistic_valgrad(const double* X, long long ldx, const double* y
                                  void* stream);
 int medp_resampled_binary_metrics(const unsigned char* y, const double* p, const int* idx, const long long* offsets, double* out,
                                   int N, int Rp, int R, int max_len, void* stream);
+
+/* ---- Temporal-usage diagnostics (analysis/diagnose_temporal_usage.py; csrc/temporal_diag.hip) -----------------------------
+ * medp_counterfactual_feats: medp_feats_to_input without augmentation for the five arrangements of ONE batch the diagnostic
+ *   compares, in one launch.  The series / times / lengths / static arguments are those of medp_feats_to_input (pointer tables
+ *   or rows of one stacked buffer; lengths or T_uniform).  sample_perm [B] int32 pairs every sample with another one;
+ *   time_perm [B, Tmax] int32: row b is a permutation of [0, T_b), Tmax >= every T_b, entries past T_b are unread.
+ *   Outputs, condition-major in the order {full, patient_shuffle, ts_shuffle, time_reverse, time_permute}:
+ *   xs_ts [5, B, Tpad, 2V+1], xs_times [5, B, Tpad], xs_static [5, B, Ds].  The reference transforms the RAW tuples and then
+ *   assembles, so with n = min(T, max_len), off = T - n of the series that supplies the rows, output step t < n holds
+ *     full            sample b,        row off + t                 times b,        static b
+ *     patient_shuffle sample perm[b],  row off + t                 times perm[b],  static perm[b]
+ *     ts_shuffle      sample perm[b],  row off + t                 times b,        static b
+ *     time_reverse    sample b,        row T_b - 1 - (off + t)     times b (not reversed), static b
+ *     time_permute    sample b,        row time_perm[b][off + t]   times b,        static b
+ *   i.e. reversal and permutation act BEFORE the truncation to the last max_len steps.  The mask column is 0, steps t >= n are 0.
+ *   ts_shuffle is defined only where lengths[perm[b]] == lengths[b] (the reference's padding goes negative otherwise): the
+ *   caller checks that; the kernel stays in bounds either way.  A sample_perm entry outside [0, B) or a time_perm entry
+ *   outside [0, T_b) is never dereferenced: the output rows that depend on it become NaN (the convention of
+ *   medp_resampled_binary_metrics).  Null pointers or non-positive sizes: rc < 0, no launch.
+ * medp_temporal_usage_summary: fus, ts [C, N, K] fp32 logits (condition 0 = full), attn [N, K, S] fp32 or null ->
+ *   prob [2, C, K, N] fp64 (fus then ts): the FP32 value 1 / (1 + exp(-clip(z, -50, 50))) widened, in the reference's own
+ *     arithmetic (numpy's float32 exp algorithm, fp32 sum and quotient: numpy's bits where it takes its x86 SIMD loop), the
+ *     convention of medp_head_scores and the label-major layout medp_resampled_binary_metrics reads;
+ *   sens [C-1, K, 3] fp64 = {mean |p_full - p_c| of fus, Pearson correlation of p_full and p_c of fus, mean |p_full - p_c| of ts}
+ *     over all N rows, centred two-pass moments; the correlation is NaN when either side has zero variance or N < 2;
+ *   entropy [K] fp64 = mean over N of -sum_s a log(max(a, 1e-12)) / max(log S, 1e-12), a = attn / max(sum_s attn, 1e-12);
+ *     unwritten when attn is null.
+ *   One workgroup per (condition, label), partial sums through LDS in a fixed tree: no floating-point atomics, two launches
+ *   are bit-identical.  One workgroup walks a label's N rows (and, for the entropy, one thread a row's S weights), hence
+ *   N <= MEDP_TEMPORAL_USAGE_MAX_N, S <= MEDP_TEMPORAL_USAGE_MAX_S and C K <= 65535: beyond them rc < 0, no launch. */
+#define MEDP_COUNTERFACTUAL_CONDITIONS 5
+#define MEDP_TEMPORAL_USAGE_MAX_N (1 << 22)
+#define MEDP_TEMPORAL_USAGE_MAX_S 4096
+int medp_counterfactual_feats(const float* const* ts_ptrs, const float* ts_base, long long ts_stride, const float* const* time_ptrs,
+                              const float* time_base, long long time_stride, const int* lengths, int T_uniform, const float* static_in,
+                              const int* sample_perm, const int* time_perm, float* xs_ts, float* xs_times, float* xs_static, int B,
+                              int V, int Ds, int max_len, int Tpad, int Tmax, void* stream);
+int medp_temporal_usage_summary(const float* fus, const float* ts, const float* attn, double* prob, double* sens, double* entropy,
+                                int C, int N, int K, int S, void* stream);
 
 /* ---- Conditional-information probe (analysis/conditional_information_probe.py; csrc/cond_probe.hip) -----------------------
  * The device half of a batched damped-Newton fit of Pipeline(StandardScaler, LogisticRegression(C)) with a free, unpenalised

@@ -106,8 +106,7 @@ __device__ __forceinline__ void row_softmax(const SmallAttnParams& p, const floa
 constexpr int FWD_QCH = 8;     // queries per workgroup of the forward kernel (two per wave)
 
 template <int NPER, bool MASKED>
-__global__ __launch_bounds__(256) void attn_small_fwd_kernel(const SmallAttnParams p, void* __restrict__ o, int ldo, int o_bf16,
-                                                             float* __restrict__ attn_avg) {
+__global__ __launch_bounds__(256) void attn_small_fwd_kernel(const SmallAttnParams p, void* __restrict__ o, int ldo, int o_bf16) {
     extern __shared__ float sm[];   // [4][Lk] probabilities, [4][dh] query row
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // (once per thread: inside the loops the epoch word was a global load per probability — 1132 us instead of ~110 for the
@@ -136,10 +135,7 @@ __global__ __launch_bounds__(256) void attn_small_fwd_kernel(const SmallAttnPara
             if (j < p.Lk) {
                 float w = pj[i];
                 if (p.drop_p > 0.f) w *= dropout_scale(mixed_seed, p.stream_id, ((uint32_t)(b * p.H + h) * p.Lq + qi) * p.Lk + j, p.drop_p, p.inv_keep);
-                sp[j] = w;
-                if constexpr (!MASKED) {      // the masked form averages the heads in attn_small_avg_kernel (one plain store per element)
-                    if (attn_avg) atomicAdd(attn_avg + ((size_t)b * p.Lq + qi) * p.Lk + j, w / (float)p.H);
-                }
+                sp[j] = w;                    // the heads are averaged in attn_small_avg_kernel (one plain store per element)
             }
         }
         WAVE_LDS_SYNC();
@@ -152,17 +148,18 @@ __global__ __launch_bounds__(256) void attn_small_fwd_kernel(const SmallAttnPara
     }
 }
 
-// attn_avg[b][q][j] = (1/H) sum_h P_bhqj dropmask_bhqj for the MASKED form: a wave per (batch, query) recomputes the row of every
-// head in turn and adds them in head order, then stores each element once — bitwise reproducible, where the atomic adds of the
-// unmasked forward are not (the order of the heads' workgroups varies).  Masked keys get exactly 0.
-template <int NPER>
+// attn_avg[b][q][j] = (1/H) sum_h P_bhqj dropmask_bhqj: a wave per (batch, query) recomputes the row of every head in turn and adds
+// them in head order, then stores each element once — bitwise reproducible, where atomic adds from the heads' workgroups were not
+// (their order varies from launch to launch; the temporal-usage diagnostics compare attention maps bit for bit).  Masked keys get
+// exactly 0.
+template <int NPER, bool MASKED>
 __global__ __launch_bounds__(256) void attn_small_avg_kernel(const SmallAttnParams p, float* __restrict__ attn_avg) {
     __shared__ float sQ[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = blockIdx.x, qi = blockIdx.y * 4 + wave;
     if (qi >= p.Lq) return;                      // whole waves leave; no block barrier below
     const uint32_t mixed_seed = p.drop_p > 0.f ? medp_mix_epoch(p.seed, p.epoch) : 0u;
-    const unsigned char* mrow = p.mask + (size_t)b * p.mask_bs;
+    const unsigned char* mrow = MASKED ? p.mask + (size_t)b * p.mask_bs : nullptr;
     float pj[NPER], acc[NPER];
 #pragma unroll
     for (int i = 0; i < NPER; ++i) acc[i] = 0.f;
@@ -171,7 +168,7 @@ __global__ __launch_bounds__(256) void attn_small_avg_kernel(const SmallAttnPara
         const bool vec = (((p.dh | p.ldk) & 3) == 0) && (((uintptr_t)kbase & 15) == 0);
         if (lane < p.dh) sQ[wave][lane] = p.q[(size_t)b * p.q_bs + (size_t)qi * p.ldq + h * p.dh + lane];
         WAVE_LDS_SYNC();
-        row_softmax<NPER, true>(p, sQ[wave], kbase, lane, pj, vec, mrow);
+        row_softmax<NPER, MASKED>(p, sQ[wave], kbase, lane, pj, vec, mrow);
 #pragma unroll
         for (int i = 0; i < NPER; ++i) {
             const int j = lane + 64 * i;
@@ -533,7 +530,7 @@ size_t fq_lds(int nchp) { return (size_t)(2 * FQ * 64 + 4 * FQ + 16 * FQ * 64 + 
 size_t small_bwd_lds(const SmallAttnParams& p) { return (size_t)(2 * QCH * p.Lk + 2 * QCH * p.dh) * sizeof(float); }
 
 // The forward of the plain and the key-masked export (p.mask chooses).  Few queries without a mask and without a head average take
-// the thread-per-key kernels; everything else a wave per query, the masked form with its head average in a launch of its own.
+// the thread-per-key kernels; everything else a wave per query, with the head average in a launch of its own.
 int small_fwd(const SmallAttnParams& p, void* o, int ldo, int o_bf16, float* attn_avg, hipStream_t st) {
     const bool masked = p.mask != nullptr;
     if (!masked && !attn_avg && fq_eligible(p, p.k, p.v, 4, 4)) {
@@ -547,13 +544,15 @@ int small_fwd(const SmallAttnParams& p, void* o, int ldo, int o_bf16, float* att
     const dim3 grid(p.B * p.H, (p.Lq + FWD_QCH - 1) / FWD_QCH);
     with_masked(masked, [&](auto MASKED) {
         with_nper(nper, [&](auto NPER) {
-            attn_small_fwd_kernel<NPER(), MASKED()><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16, masked ? nullptr : attn_avg);
+            attn_small_fwd_kernel<NPER(), MASKED()><<<grid, 256, lds, st>>>(p, o, ldo, o_bf16);
         });
     });
     MEDP_LAUNCH_CHECK(masked ? "medp_attn_small_masked_fwd" : "medp_attn_small_fwd");
-    if (masked && attn_avg) {
-        with_nper(nper, [&](auto NPER) { attn_small_avg_kernel<NPER()><<<dim3(p.B, (p.Lq + 3) / 4), 256, 0, st>>>(p, attn_avg); });
-        MEDP_LAUNCH_CHECK("medp_attn_small_masked_fwd(attn_avg)");
+    if (attn_avg) {
+        with_masked(masked, [&](auto MASKED) {
+            with_nper(nper, [&](auto NPER) { attn_small_avg_kernel<NPER(), MASKED()><<<dim3(p.B, (p.Lq + 3) / 4), 256, 0, st>>>(p, attn_avg); });
+        });
+        MEDP_LAUNCH_CHECK(masked ? "medp_attn_small_masked_fwd(attn_avg)" : "medp_attn_small_fwd(attn_avg)");
     }
     return 0;
 }

@@ -216,30 +216,23 @@ class Model(nn.Module):
             cache[key] = torch.tensor(list(values), dtype=dtype, device=self.device)
         return cache[key]
 
-    def feats_to_input(self, x, batch_size, limits=None):
-        """Same contract as duett.py:159-187: (tuples of per-sample tensors) -> (xs_static [B,Ds], xs_ts [B,Tpad,2V+1],
-        xs_times [B,Tpad], n_timesteps) — ONE launch of `medp_feats_to_input` instead of the host loop over the batch:
-        truncation to the last max_len steps, the mask column, zero padding to the longest series and the training
-        augmentation all happen on the device (SURVEY.md §8(f3)).  Inputs may live on the host (one concatenated upload) or on
-        the device (rows of one stacked buffer: no copy at all; separate tensors: a pointer table).  With augmentation off the
-        result is bit-identical to the reference's; with it on the draws come from the library's counter RNG, not torch's.
-        Unlike the reference the caller's tensors are never modified in place."""
+    def _locate_batch(self, x, what="feats_to_input"):
+        """Where the batch assembly kernels find the per-sample tensors: -> (args, lens, keep, (B, V, Ds)).  `args` are the first nine
+        arguments of `medp_feats_to_input` / `medp_counterfactual_feats` (series table | base, stride; times table | base, stride;
+        lengths table, uniform length; static [B, Ds]), `lens` the original lengths, `keep` the temporaries the launch reads.
+        Host tensors: one concatenated upload; rows of one stacked device buffer: no copy; separate device tensors: a pointer table."""
         abi.require_gpu()
         xs_ts, xs_static, times = x
         xs_ts, xs_static, times = list(xs_ts), list(xs_static), list(times)
         dev = self.device
         if dev.type != "cuda":
-            raise RuntimeError("feats_to_input: the model is on %s; the batch assembly kernel needs the GPU (no CPU fallback)" % dev)
+            raise RuntimeError("%s: the model is on %s; the batch assembly kernel needs the GPU (no CPU fallback)" % (what, dev))
         B = len(xs_ts)
         V2 = int(xs_ts[0].shape[1])
         V, Ds = V2 // 2, int(xs_static[0].shape[0])
         lens = [int(f.shape[0]) for f in xs_ts]
         if any(int(t.shape[0]) != n for t, n in zip(times, lens)) or any(int(f.shape[1]) != V2 for f in xs_ts):
-            raise ValueError("feats_to_input: every series needs [T_i, 2V] features and [T_i] times")
-        n_timesteps = [min(n, self.max_len) for n in lens]
-        Tpad = max(n_timesteps)
-        aug = self.training and not self.pretrain
-        noise, maskp = (float(self.aug_noise), float(self.aug_mask)) if aug else (0.0, 0.0)
+            raise ValueError("%s: every series needs [T_i, 2V] features and [T_i] times" % what)
         keep = []                                   # temporaries the launch reads
 
         def locate(ts, width):
@@ -272,16 +265,33 @@ class Model(nn.Module):
             static_ptr = st.data_ptr()
         uniform = len(set(lens)) == 1
         len_tab = None if uniform else self._device_table(lens, torch.int32)
-        out_ts = torch.empty((B, Tpad, V2 + 1), dtype=torch.float32, device=dev)
+        args = (ptr(ts_tab), ts_base, ts_stride, ptr(tm_tab), tm_base, tm_stride, ptr(len_tab), lens[0] if uniform else 0, static_ptr)
+        return args, lens, keep, (B, V, Ds)
+
+    def feats_to_input(self, x, batch_size, limits=None):
+        """Same contract as duett.py:159-187: (tuples of per-sample tensors) -> (xs_static [B,Ds], xs_ts [B,Tpad,2V+1],
+        xs_times [B,Tpad], n_timesteps) — ONE launch of `medp_feats_to_input` instead of the host loop over the batch:
+        truncation to the last max_len steps, the mask column, zero padding to the longest series and the training
+        augmentation all happen on the device (SURVEY.md §8(f3)).  Inputs may live on the host (one concatenated upload) or on
+        the device (rows of one stacked buffer: no copy at all; separate tensors: a pointer table).  With augmentation off the
+        result is bit-identical to the reference's; with it on the draws come from the library's counter RNG, not torch's.
+        Unlike the reference the caller's tensors are never modified in place."""
+        where, lens, keep, (B, V, Ds) = self._locate_batch(x)
+        dev = self.device
+        n_timesteps = [min(n, self.max_len) for n in lens]
+        Tpad = max(n_timesteps)
+        aug = self.training and not self.pretrain
+        noise, maskp = (float(self.aug_noise), float(self.aug_mask)) if aug else (0.0, 0.0)
+        out_ts = torch.empty((B, Tpad, 2 * V + 1), dtype=torch.float32, device=dev)
         out_tm = torch.empty((B, Tpad), dtype=torch.float32, device=dev)
         out_st = torch.empty((B, Ds), dtype=torch.float32, device=dev)
         seed = 0
         if noise > 0 or maskp > 0:
             from . import autograd_ops as A
             seed = A.next_seed()
-        check(lib().medp_feats_to_input(ptr(ts_tab), ts_base, ts_stride, ptr(tm_tab), tm_base, tm_stride, ptr(len_tab),
-                                        lens[0] if uniform else 0, static_ptr, ptr(out_ts), ptr(out_tm), ptr(out_st), B, V, Ds,
+        check(lib().medp_feats_to_input(*where, ptr(out_ts), ptr(out_tm), ptr(out_st), B, V, Ds,
                                         int(self.max_len), Tpad, noise, maskp, seed, self._FEATS_SID, stream()), "feats_to_input")
+        del keep
         return out_st, out_ts, out_tm, n_timesteps
 
     # ------------------------------------------------------------------------------------------ weight preparation

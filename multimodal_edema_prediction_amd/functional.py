@@ -290,7 +290,7 @@ def attn_dh16_train_bwd(dout: torch.Tensor, qkv: torch.Tensor, lse: torch.Tensor
 def attn_small_fwd(q, k, v, B, Lq, Lk, H, dh, scale, *, q_batch_stride=None, kv_batch_stride=None, out_dtype=F32,
                    dropout_p=0.0, seed=0, stream_id=0, attn_avg=None, key_mask=None):
     """q fp32 rows [.., H*dh] (ld = q.stride(-2)); k, v fp32 with a common row stride.  `key_mask`: uint8 [B, Lk], non-zero =
-    key ignored (the masked kernels; `attn_avg` then need not be zeroed)."""
+    key ignored (the masked kernels).  `attn_avg` need not be zeroed: every element is written once, heads added in order."""
     ldq, ldkv = q.stride(-2), k.stride(-2)
     assert v.stride(-2) == ldkv
     qbs = Lq * ldq if q_batch_stride is None else q_batch_stride

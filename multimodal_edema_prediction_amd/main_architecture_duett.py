@@ -313,10 +313,9 @@ class TeacherModel(nn.Module):
                 p.requires_grad = False
             self.register_buffer("cxr_head_keep_idx", torch.tensor(keep_idx, dtype=torch.long))
 
-    def _dual_forward(self, duett_in, pixel_values, return_attn):
-        """model file :1132-1150: CLS -> frozen pretrained head -> the K kept columns -> DualPathologyPerceiver.  Only the kept
-        rows of the head are multiplied (the same numbers as computing all C columns and gathering K of them)."""
-        ts_tokens = self.duett.encode(duett_in)
+    def _kept_head_logits(self, pixel_values):
+        """CLS -> frozen pretrained head -> the K kept columns (model file :1132-1141).  Only the kept rows of the head are multiplied
+        (the same numbers as computing all C columns and gathering K of them)."""
         cls = self.cxr(pixel_values)
         if isinstance(cls, tuple):
             cls = cls[0]
@@ -330,7 +329,12 @@ class TeacherModel(nn.Module):
                 W[:K], b[:K] = head.weight[self.cxr_head_keep_idx], head.bias[self.cxr_head_keep_idx]
                 self._kept_head = (key, W, b)
             _, W, b = self._kept_head
-            img_logits = A.linear(cls.contiguous(), W, b)[:, :K].contiguous()
+            return A.linear(cls.contiguous(), W, b)[:, :K].contiguous()
+
+    def _dual_forward(self, duett_in, pixel_values, return_attn):
+        """model file :1132-1150: the kept-head image logits -> DualPathologyPerceiver."""
+        ts_tokens = self.duett.encode(duett_in)
+        img_logits = self._kept_head_logits(pixel_values)
         out = self.perceiver(ts_tokens, img_logits, return_attn=return_attn)
         result = {"main_logit": out["fusion_logits"][:, 0], "img_logits": out["img_logits"], "ts_logits": out["ts_logits"],
                   "fusion_logits": out["fusion_logits"]}
