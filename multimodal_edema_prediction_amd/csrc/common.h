@@ -108,6 +108,21 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// Sum over a 256-thread workgroup in a fixed order, in two pieces around the caller's own __syncthreads(): each wave's butterfly
+// sum goes to red[wave]; after the barrier sum4 adds the four as (0+1)+(2+3) in whichever threads need the total.
+__device__ __forceinline__ void wave_sums_to_lds(float v, float* red) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+}
+__device__ __forceinline__ void wave_sums_to_lds(float a, float b, float (*red)[4]) {        // two quantities: red[0][wave], red[1][wave]
+    a = wave_sum(a);
+    b = wave_sum(b);
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = a;
+        red[1][threadIdx.x >> 6] = b;
+    }
+}
+__device__ __forceinline__ float sum4(const float* red) { return (red[0] + red[1]) + (red[2] + red[3]); }
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

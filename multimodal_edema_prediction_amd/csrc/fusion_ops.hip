@@ -1,4 +1,4 @@
-// Pointwise / tiny-reduction kernels of the cross-modal fusion head and of the losses (gfx950).
+// Pointwise / tiny-reduction kernels of the cross-modal fusion head (gfx950); the losses are in losses.hip.
 // Everything here is launch-bound ([B,7] logits, [B*7,256] latents): the point is ONE launch per logical op, fp32
 // math identical to the reference, and dropout masks that are regenerated (not stored) in backward.
 #include "common.h"
@@ -140,114 +140,6 @@ __global__ __launch_bounds__(64) void fusion_logits_bwd_kernel(const float* __re
     d_beta[k] = sbe;
 }
 
-// ---- DualPathologyLoss (loss/losses_duett.py:131-194) forward + gradient in ONE single-block launch -------------------
-// per branch r, label k:  per[r][k] = sum_b bce(l_bk, y_bk [,pos_weight_k]) * m_bk / (sum_b m_bk + eps)
-// branch_total[r] = sum_k w_k per[r][k];  total = sum_r alpha_r branch_total[r]
-// grad[r][b][k] = alpha_r * w_k * m_bk / (sum_b m_bk + eps) * dbce/dl
-// out: [0] total, [1..3] branch totals, [4 .. 4+3K) per-label losses (img | ts | fus)
-__device__ __forceinline__ float softplus_neg(float l) { return fmaxf(-l, 0.f) + log1pf(__expf(-fabsf(l))); }   // log(1+exp(-l))
-__global__ __launch_bounds__(256) void dual_loss_kernel(const float* __restrict__ img, const float* __restrict__ ts,
-                                                        const float* __restrict__ fus, const float* __restrict__ y,
-                                                        const float* __restrict__ mask, const float* __restrict__ lw,
-                                                        const float* __restrict__ pw, float a_img, float a_ts, float a_fus, float eps,
-                                                        float* __restrict__ out, float* __restrict__ g_img, float* __restrict__ g_ts,
-                                                        float* __restrict__ g_fus, int B, int K) {
-    __shared__ float s_per[3][32];
-    __shared__ float s_den[32];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* L[3] = {img, ts, fus};
-    // wave w handles labels w, w+4, ...
-    for (int k = wave; k < K; k += 4) {
-        float den = 0.f, acc[3] = {0.f, 0.f, 0.f};
-        const float pwk = pw ? pw[k] : 1.f;
-        for (int b = lane; b < B; b += 64) {
-            const float m = mask[b * K + k], yy = y[b * K + k];
-            den += m;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const float l = L[r][b * K + k];
-                // BCEWithLogits with pos_weight: (1-y)*l + (1 + (pw-1)*y) * log(1+exp(-l))
-                acc[r] += ((1.f - yy) * l + (1.f + (pwk - 1.f) * yy) * softplus_neg(l)) * m;
-            }
-        }
-        den = wave_sum(den);
-#pragma unroll
-        for (int r = 0; r < 3; ++r) acc[r] = wave_sum(acc[r]);
-        if (lane == 0) {
-            s_den[k] = den + eps;
-#pragma unroll
-            for (int r = 0; r < 3; ++r) s_per[r][k] = acc[r] / (den + eps);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float tot[3] = {0.f, 0.f, 0.f};
-        for (int r = 0; r < 3; ++r)
-            for (int k = 0; k < K; ++k) {
-                tot[r] += lw[k] * s_per[r][k];
-                out[4 + r * K + k] = s_per[r][k];
-            }
-        out[0] = a_img * tot[0] + a_ts * tot[1] + a_fus * tot[2];
-        out[1] = tot[0];
-        out[2] = tot[1];
-        out[3] = tot[2];
-    }
-    float* G[3] = {g_img, g_ts, g_fus};
-    const float A[3] = {a_img, a_ts, a_fus};
-    for (int i = threadIdx.x; i < B * K; i += 256) {
-        const int k = i % K;
-        const float m = mask[i], yy = y[i], pwk = pw ? pw[k] : 1.f;
-        const float c = lw[k] * m / s_den[k];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            if (!G[r]) continue;
-            const float l = L[r][i];
-            const float sg = 1.f / (1.f + __expf(-l));
-            // d/dl [(1-y) l + (1+(pw-1)y) softplus(-l)] = (1-y) - (1+(pw-1)y)(1-sigmoid(l))
-            G[r][i] = A[r] * c * ((1.f - yy) - (1.f + (pwk - 1.f) * yy) * (1.f - sg));
-        }
-    }
-}
-
-// ---- StudentKDLoss (losses_duett.py:8-57): total = alpha*BCE(z_s,y) + (1-alpha)*T^2*mean KL(sig(z_t/T) || sig(z_s/T)) ----
-// out: [0] total [1] bce [2] kd ; grad wrt z_s
-__global__ __launch_bounds__(256) void kd_loss_kernel(const float* __restrict__ zs, const float* __restrict__ zt, const float* __restrict__ y,
-                                                      float T, float alpha, float pos_weight, float eps, float* __restrict__ out,
-                                                      float* __restrict__ g, int B) {
-    __shared__ float red[2][4];
-    float bce = 0.f, kl = 0.f;
-    for (int b = threadIdx.x; b < B; b += 256) {
-        const float l = zs[b], yy = y[b];
-        bce += (1.f - yy) * l + (1.f + (pos_weight - 1.f) * yy) * softplus_neg(l);
-        float pt = 1.f / (1.f + __expf(-zt[b] / T)), ps = 1.f / (1.f + __expf(-l / T));
-        const float psc = fminf(fmaxf(ps, eps), 1.f - eps);
-        pt = fminf(fmaxf(pt, eps), 1.f - eps);
-        kl += pt * (logf(pt) - logf(psc)) + (1.f - pt) * (logf(1.f - pt) - logf(1.f - psc));
-        if (g) {
-            const float sg = 1.f / (1.f + __expf(-l));
-            const float dbce = (1.f - yy) - (1.f + (pos_weight - 1.f) * yy) * (1.f - sg);
-            // d kl / d ps = -pt/ps + (1-pt)/(1-ps) (zero where the clamp is active); d ps / d l = ps(1-ps)/T
-            const float inside = (ps > eps && ps < 1.f - eps) ? 1.f : 0.f;
-            const float dkl = inside * (-pt / psc + (1.f - pt) / (1.f - psc)) * ps * (1.f - ps) / T;
-            g[b] = (alpha * dbce + (1.f - alpha) * T * T * dkl) / (float)B;
-        }
-    }
-    bce = wave_sum(bce);
-    kl = wave_sum(kl);
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = bce;
-        red[1][threadIdx.x >> 6] = kl;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float b_ = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (float)B;
-        const float k_ = T * T * ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)B;
-        out[0] = alpha * b_ + (1.f - alpha) * k_;
-        out[1] = b_;
-        out[2] = k_;
-    }
-}
-
 // mean over the first T tokens of [B, T+1, D] (StudentModel pool="mean", model :1231) and its backward
 __global__ __launch_bounds__(256) void meanpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int T, int T1, int D) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < B * D; i += gridDim.x * 256) {
@@ -263,68 +155,6 @@ __global__ __launch_bounds__(256) void meanpool_bwd_kernel(const float* __restri
         const int d = (int)(i % D), t = (int)((i / D) % T1), b = (int)(i / ((size_t)D * T1));
         dx[i] = t < T ? dy[(size_t)b * D + d] / (float)T : 0.f;
     }
-}
-
-// ---- engine extras (training_duett/engine.py:149-165, 217-223) and the linear-probe loss (cxr_linear_training.ipynb:426-437) ----
-// aux residual KL: KL(Bern(y_smooth) || Bern(sigmoid(img.detach() + scaled))) masked mean; grad wrt `scaled` only.
-__global__ __launch_bounds__(256) void aux_kl_kernel(const float* __restrict__ img, const float* __restrict__ scaled, const float* __restrict__ y,
-                                                     const float* __restrict__ mask, float smooth, float* __restrict__ out,
-                                                     float* __restrict__ g, int n) {
-    __shared__ float red[2][4];
-    float num = 0.f, den = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const float ys = y[i] * (1.f - smooth) + (1.f - y[i]) * smooth;
-        const float pr = 1.f / (1.f + __expf(-(img[i] + scaled[i])));
-        const float p = fminf(fmaxf(pr, 1e-6f), 1.f - 1e-6f);
-        num += (ys * (logf(ys) - logf(p)) + (1.f - ys) * (logf(1.f - ys) - logf(1.f - p))) * mask[i];
-        den += mask[i];
-    }
-    num = wave_sum(num);
-    den = wave_sum(den);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = num; red[1][threadIdx.x >> 6] = den; }
-    __syncthreads();
-    const float D = fmaxf((red[1][0] + red[1][1]) + (red[1][2] + red[1][3]), 1.f);
-    if (threadIdx.x == 0) out[0] = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / D;
-    if (g) {
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const float ys = y[i] * (1.f - smooth) + (1.f - y[i]) * smooth;
-            const float pr = 1.f / (1.f + __expf(-(img[i] + scaled[i])));
-            const float inside = (pr > 1e-6f && pr < 1.f - 1e-6f) ? 1.f : 0.f;
-            const float p = fminf(fmaxf(pr, 1e-6f), 1.f - 1e-6f);
-            g[i] = inside * (-ys / p + (1.f - ys) / (1.f - p)) * pr * (1.f - pr) * mask[i] / D;
-        }
-    }
-}
-// out = coef * mean(x^2), g = 2*coef*x/n        (LP regularisers beta_l2*mean(beta^2), corr_l2*mean(scaled^2))
-__global__ __launch_bounds__(256) void sq_mean_kernel(const float* __restrict__ x, float coef, float* __restrict__ out, float* __restrict__ g, int n) {
-    __shared__ float red[4];
-    float a = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        a += x[i] * x[i];
-        if (g) g[i] = 2.f * coef * x[i] / (float)n;
-    }
-    a = wave_sum(a);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = coef * ((red[0] + red[1]) + (red[2] + red[3])) / (float)n;
-}
-// one global masked mean: sum(bce*m)/max(sum(m),1)   (config 2 linear probe)
-__global__ __launch_bounds__(256) void masked_bce_kernel(const float* __restrict__ l, const float* __restrict__ y, const float* __restrict__ mask,
-                                                         float* __restrict__ out, float* __restrict__ g, int n) {
-    __shared__ float red[2][4];
-    float num = 0.f, den = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        num += ((1.f - y[i]) * l[i] + softplus_neg(l[i])) * mask[i];
-        den += mask[i];
-    }
-    num = wave_sum(num);
-    den = wave_sum(den);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = num; red[1][threadIdx.x >> 6] = den; }
-    __syncthreads();
-    const float D = fmaxf((red[1][0] + red[1][1]) + (red[1][2] + red[1][3]), 1.f);
-    if (threadIdx.x == 0) out[0] = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / D;
-    if (g)
-        for (int i = threadIdx.x; i < n; i += 256) g[i] = (1.f / (1.f + __expf(-l[i])) - y[i]) * mask[i] / D;
 }
 
 }  // namespace
@@ -391,24 +221,6 @@ extern "C" int medp_fusion_logits_bwd(const float* d_img, const float* d_ts, con
     MEDP_LAUNCH_CHECK("medp_fusion_logits_bwd");
     return 0;
 }
-extern "C" int medp_dual_pathology_loss(const float* img, const float* ts, const float* fus, const float* y, const float* mask,
-                                        const float* label_weights, const float* pos_weight, float alpha_img, float alpha_ts,
-                                        float alpha_fus, float eps, float* out, float* g_img, float* g_ts, float* g_fus, int B, int K,
-                                        void* stream) {
-    MEDP_CHECK_ARG(img && ts && fus && y && mask && label_weights && out, "dual_pathology_loss: null argument");
-    MEDP_CHECK_ARG(B > 0 && K > 0 && K <= 32, "dual_pathology_loss: need 0 < K <= 32 (got %d)", K);
-    dual_loss_kernel<<<1, 256, 0, (hipStream_t)stream>>>(img, ts, fus, y, mask, label_weights, pos_weight, alpha_img, alpha_ts, alpha_fus, eps,
-                                                         out, g_img, g_ts, g_fus, B, K);
-    MEDP_LAUNCH_CHECK("medp_dual_pathology_loss");
-    return 0;
-}
-extern "C" int medp_student_kd_loss(const float* z_s, const float* z_t, const float* y, float T, float alpha, float pos_weight,
-                                    float* out, float* g_zs, int B, void* stream) {
-    MEDP_CHECK_ARG(z_s && z_t && y && out && B > 0 && T > 0.f, "student_kd_loss: bad argument");
-    kd_loss_kernel<<<1, 256, 0, (hipStream_t)stream>>>(z_s, z_t, y, T, alpha, pos_weight, 1e-7f, out, g_zs, B);
-    MEDP_LAUNCH_CHECK("medp_student_kd_loss");
-    return 0;
-}
 extern "C" int medp_meanpool_fwd(const float* x, float* y, int B, int T, int T1, int D, void* stream) {
     MEDP_CHECK_ARG(x && y && B > 0 && T > 0 && T1 >= T && D > 0, "meanpool_fwd: bad argument");
     meanpool_fwd_kernel<<<grid_for((size_t)B * D, GRID_CAP), 256, 0, (hipStream_t)stream>>>(x, y, B, T, T1, D);
@@ -419,26 +231,6 @@ extern "C" int medp_meanpool_bwd(const float* dy, float* dx, int B, int T, int T
     MEDP_CHECK_ARG(dy && dx && B > 0 && T > 0 && T1 >= T && D > 0, "meanpool_bwd: bad argument");
     meanpool_bwd_kernel<<<grid_for((size_t)B * T1 * D, GRID_CAP), 256, 0, (hipStream_t)stream>>>(dy, dx, B, T, T1, D);
     MEDP_LAUNCH_CHECK("medp_meanpool_bwd");
-    return 0;
-}
-
-extern "C" int medp_aux_residual_kl(const float* img_logits, const float* scaled_correction, const float* y, const float* mask,
-                                    float label_smoothing, float* out, float* g_scaled, int n, void* stream) {
-    MEDP_CHECK_ARG(img_logits && scaled_correction && y && mask && out && n > 0, "aux_residual_kl: bad argument");
-    aux_kl_kernel<<<1, 256, 0, (hipStream_t)stream>>>(img_logits, scaled_correction, y, mask, label_smoothing, out, g_scaled, n);
-    MEDP_LAUNCH_CHECK("medp_aux_residual_kl");
-    return 0;
-}
-extern "C" int medp_sq_mean(const float* x, float coef, float* out, float* g, int n, void* stream) {
-    MEDP_CHECK_ARG(x && out && n > 0, "sq_mean: bad argument");
-    sq_mean_kernel<<<1, 256, 0, (hipStream_t)stream>>>(x, coef, out, g, n);
-    MEDP_LAUNCH_CHECK("medp_sq_mean");
-    return 0;
-}
-extern "C" int medp_masked_bce_global(const float* logits, const float* y, const float* mask, float* out, float* g, int n, void* stream) {
-    MEDP_CHECK_ARG(logits && y && mask && out && n > 0, "masked_bce_global: bad argument");
-    masked_bce_kernel<<<1, 256, 0, (hipStream_t)stream>>>(logits, y, mask, out, g, n);
-    MEDP_LAUNCH_CHECK("medp_masked_bce_global");
     return 0;
 }
 

@@ -253,10 +253,9 @@ __global__ __launch_bounds__(256) void sum_all_kernel(const float* __restrict__ 
     __shared__ float red[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) s += v[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    wave_sums_to_lds(s, red);
     __syncthreads();
-    if (threadIdx.x == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (threadIdx.x == 0) out[0] = sum4(red);
 }
 
 int colsum_chunks(int rows) { return max(1, min(128, rows / 64)); }

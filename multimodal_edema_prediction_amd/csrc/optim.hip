@@ -72,14 +72,6 @@ __global__ __launch_bounds__(256) void adamw_multi_dscale_kernel(const MedpAdamT
 }
 #undef MEDP_ADAMW_BODY
 
-// 256 values -> their sum in every thread, in a fixed order (wave butterflies, then the four wave sums left to right)
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // Global gradient norm, pass 1: workgroup b (the SAME block map as the update) writes the sum of squares of its chunk.
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(const MedpAdamTensor* __restrict__ descs, const int* __restrict__ blk_tensor,
                                                          const int* __restrict__ blk_chunk, float* __restrict__ partials) {
@@ -97,8 +89,9 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const MedpAdamTensor* _
     } else {
         for (long long i = base + threadIdx.x; i < end; i += 256) acc += g[i] * g[i];
     }
-    acc = block_sum_256(acc, red);
-    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
+    wave_sums_to_lds(acc, red);
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = sum4(red);
 }
 
 // pass 2, ONE workgroup: the partials summed in index order (thread t takes t, t + 256, ...; then the fixed block reduction; fp64,

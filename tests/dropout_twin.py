@@ -1,10 +1,10 @@
 """Host replica of the dropout masks the HIP kernels draw (a test helper, like helpers.py), bit for bit.
 
 Restates, in numpy uint32 arithmetic with wrap-around:
-  * `medp_mix_epoch`  (multimodal_edema_prediction_amd/csrc/common.h:72): seed + epoch * 0x9E3779B9, or the seed itself when no epoch
+  * `medp_mix_epoch`  (multimodal_edema_prediction_amd/csrc/common.h:89): seed + epoch * 0x9E3779B9, or the seed itself when no epoch
     counter is registered (medp_rng_set_epoch_ptr(NULL));
-  * `medp_hash`       (common.h:171-176): one 32-bit hash per (seed, stream id, element index);
-  * `dropout_scale`   (common.h:178-181): keep iff (h >> 8) * 2^-24 >= p in fp32, kept elements scaled by 1 / (1 - p);
+  * `medp_hash`       (common.h:203-208): one 32-bit hash per (seed, stream id, element index);
+  * `dropout_scale`   (common.h:210-213): keep iff (h >> 8) * 2^-24 >= p in fp32, kept elements scaled by 1 / (1 - p);
   * the fp32 scale every launcher passes, `1.f / (1.f - p)` (fusion_ops.hip, attention_small.hip, attention_fq_split.hip,
     attention_dh16.hip);
   * the element index of each layout: the flat index of a contiguous tensor (fusion_ops.hip: gelu_dropout_*, dropout_add) and

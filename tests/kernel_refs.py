@@ -1,4 +1,4 @@
-"""Plain torch restatements that the kernel-level tests of fusion_ops.hip, ssl_ops.hip and duett_train.hip compare against, for the
+"""Plain torch restatements that the kernel-level tests of losses.hip and duett_train.hip compare against, for the
 cases the oracle does not state in a callable form: losses whose clamp bounds must be the kernels' fp32 constants, and the pieces of
 `duett_ref.build_psi` that the training glue computes one kernel at a time.  Every function works in the dtype of its inputs (the
 GPU tests hand it float64) and is differentiable, so gradients come from autograd.  tests/test_kernel_refs_cpu.py shows that each

@@ -1,4 +1,4 @@
-"""Every loss kernel of csrc/fusion_ops.hip and csrc/ssl_ops.hip on its own, through the project's wrappers, against the same loss in
+"""Every loss kernel of csrc/losses.hip on its own, through the project's wrappers, against the same loss in
 float64 on the CPU (oracle/losses_ref.py, or the restatements of tests/kernel_refs.py that test_kernel_refs_cpu.py ties to the
 oracle) with float64 autograd for the gradients — at sizes where every loop takes a second trip (64 lanes over B, 4 waves over K,
 256 threads over n) and in the branches the model-level fixtures never enter: pos_weight, a fully masked label, saturated logits
