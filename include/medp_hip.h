@@ -556,6 +556,33 @@ int medp_counterfactual_feats(const float* const* ts_ptrs, const float* ts_base,
 int medp_temporal_usage_summary(const float* fus, const float* ts, const float* attn, double* prob, double* sens, double* entropy,
                                 int C, int N, int K, int S, void* stream);
 
+/* ---- Modality complementarity (analysis/complementarity.py; csrc/complementarity.hip) --------------------------------------
+ * medp_youden_thresholds: scores [H, N, K] fp32 (H heads stacked: img, ts, fus), y, mask [N, K] fp32 ->
+ *   thr, youden_j [H, K] fp64: `_youden_threshold` (:103-108), thr[argmax(tpr - fpr)] of sklearn's roc_curve(y, score) over the
+ *     rows with mask != 0, and the J reached there;  counts [K, 2] int32 = {known rows, known positives (y != 0)}.
+ *   One workgroup per (head, label): the known rows are compacted into LDS, sorted descending, one ROC point per DISTINCT score
+ *   (-0.0 and +0.0 are one score; a zero threshold carries the sign of the first known row that holds a zero, which is what
+ *   sklearn's stable sort reports).  Three properties of roc_curve + argmax are reproduced:
+ *     start point    (0, 0) at threshold +inf comes first and argmax keeps the FIRST maximum: no point with J > 0 -> thr = +inf, J = 0;
+ *     arithmetic     J = (double)tp / P - (double)fp / Nneg, two rounded fp64 quotients and one difference, compared as such;
+ *     dropped points drop_intermediate: an interior point g (0 < g < G-1) whose second differences of tp AND fp are zero is skipped.
+ *   The argmax is a fixed-tree reduction on (J, point index), larger J first, then the lower index: two launches are bit-identical.
+ *   Fewer than two known rows or one class only: thr = J = NaN.  A non-finite score among the known rows: thr = J = NaN.
+ *   The sort stages 8-byte keys in LDS (the arithmetic of medp_resampled_binary_metrics): a label with more than
+ *   MEDP_YOUDEN_MAX_LEN known rows gives rc < 0 and the threshold kernel is not launched (for N above the bound the known rows are
+ *   counted on the device first and read back: one synchronisation, and `counts` is already written).  Null pointers or
+ *   non-positive sizes: rc < 0, no launch.
+ * medp_complementarity_cells: scores [3, N, K] fp32, y, mask [N, K] fp32, thr [3, K] fp64 -> cells [K, 16] int32: over the rows
+ *   with mask != 0 the count of every combination  (y != 0) | ip << 1 | tp << 2 | fp << 3,  ip / tp / fp = (double)score > thr of the
+ *   image / TS / fusion head (numpy's float32 > float64; a NaN or +inf threshold predicts False: `_binarize` :126-135).  Integer
+ *   counts only (LDS histograms, integer atomics into the zeroed output): deterministic.  Everything `_analyze_pathology` and
+ *   `_plot_venn` report is a function of these 16 integers.  Null pointers or non-positive sizes: rc < 0, no launch. */
+#define MEDP_YOUDEN_MAX_LEN 16384 /* 8-byte keys: 128 KiB of the CU's 160 KiB LDS, a power of two for the bitonic sort */
+int medp_youden_thresholds(const float* scores, const float* y, const float* mask, double* thr, double* youden_j, int* counts, int H,
+                           int N, int K, void* stream);
+int medp_complementarity_cells(const float* scores, const float* y, const float* mask, const double* thr, int* cells, int N, int K,
+                               void* stream);
+
 /* ---- Conditional-information probe (analysis/conditional_information_probe.py; csrc/cond_probe.hip) -----------------------
  * The device half of a batched damped-Newton fit of Pipeline(StandardScaler, LogisticRegression(C)) with a free, unpenalised
  * intercept.  All arithmetic is fp64; no floating-point atomics; every reduction runs in a fixed order (two launches are
