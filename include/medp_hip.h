@@ -583,6 +583,35 @@ int medp_youden_thresholds(const float* scores, const float* y, const float* mas
 int medp_complementarity_cells(const float* scores, const float* y, const float* mask, const double* thr, int* cells, int N, int K,
                                void* stream);
 
+/* ---- Trajectory-availability audit (analysis/trajectory_availability.py; csrc/trajectory_audit.hip) -----------------------
+ * medp_trajectory_cells: x [n, T, 2V] fp32 (values | counts, the layout medp_raw_traj_summary reads); a cell is observed iff its
+ *   count > 0.  For sample n0 + i and variable v, into variable-major planes [V, ld] (ld >= n0 + n):
+ *     obs_hours int32        the number of observed hours;
+ *     total fp32             the sum of ALL counts over t, in t order;
+ *     recency fp32           n_timesteps - last observed t (n_timesteps need not equal T), NaN if never observed;
+ *     within_std fp32        population std (ddof 0) of the observed values, fp64 two-pass, rounded ONCE to fp32; NaN below two hours;
+ *     endpoint_change fp32   value[last] - value[first], one fp32 subtraction; NaN below two observed hours;
+ *   per_sample [ld, 4] int32 = {#v with >= 1, >= 2, >= 3 observed hours, sum_v obs_hours}: rows [n0, n0 + n) are cleared, then summed;
+ *   var_counts [V, 4] int64  = {#samples >= 1, >= 2, >= 3, sum obs_hours}: ADDED to a buffer the caller zeroed before the first chunk.
+ *   The value of an unobserved cell enters no figure (NaN / inf there do not leak).  The n0 / ld pair lets a caller stream a
+ *   dataset through in chunks and end with full columns: every (sample, variable) is computed by one thread from its own cells, so
+ *   chunked calls give bit-identical planes to one call.  Only integer atomics (one per row, figure and workgroup): two launches
+ *   are bit-identical.  Null pointers, non-positive sizes, n0 < 0 or ld < n0 + n: rc < 0, no launch.
+ * medp_column_medians: n_cols columns of length N at stride ld (elements), fp32 or int32 (is_int32), optionally |.| first
+ *   (take_abs) -> median [n_cols] fp64, n_valid [n_cols] int32: what numpy reports.  NaNs are dropped (np.nanmedian); with m valid
+ *   entries and a, b the values at sorted ranks (m-1)/2 and m/2: fp32 columns give (float)(a + b) * 0.5f widened to fp64 (m odd: a
+ *   itself, numpy averages one element), int32 columns (a + b) / 2.0 in fp64; m = 0 gives NaN.  One workgroup per column selects
+ *   rank (m-1)/2 by radix: four 8-bit passes over order-preserving uint32 keys, an LDS histogram per wave, integer atomics; b is
+ *   a unless rank m/2 lies past the copies of a, then one more pass finds the smallest key above a.  Nothing is sorted or staged
+ *   in LDS, the column is re-read each pass: exact and deterministic for any N <= MEDP_COLUMN_MEDIAN_MAX_N.  -0.0 sorts below
+ *   +0.0.  Null pointers, non-positive sizes, ld < N or N above the bound: rc < 0, no launch. */
+#define MEDP_COLUMN_MEDIAN_MAX_N (1 << 30) /* every counter is 32-bit unsigned, element offsets are 64-bit */
+int medp_trajectory_cells(const float* x, int n, int T, int V, int n_timesteps, int n0, long long ld, int* obs_hours, float* total,
+                          float* recency, float* within_std, float* endpoint_change, int* per_sample, long long* var_counts,
+                          void* stream);
+int medp_column_medians(const void* planes, long long ld, int n_cols, int N, int is_int32, int take_abs, double* median, int* n_valid,
+                        void* stream);
+
 /* ---- Conditional-information probe (analysis/conditional_information_probe.py; csrc/cond_probe.hip) -----------------------
  * The device half of a batched damped-Newton fit of Pipeline(StandardScaler, LogisticRegression(C)) with a free, unpenalised
  * intercept.  All arithmetic is fp64; no floating-point atomics; every reduction runs in a fixed order (two launches are

@@ -198,6 +198,8 @@ SIGNATURES = {
     "medp_temporal_usage_summary": (I, [P, P, P, P, P, P, I, I, I, I, P]),
     "medp_youden_thresholds": (I, [P, P, P, P, P, P, I, I, I, P]),
     "medp_complementarity_cells": (I, [P, P, P, P, P, I, I, P]),
+    "medp_trajectory_cells": (I, [P, I, I, I, I, I, LL, P, P, P, P, P, P, P, P]),
+    "medp_column_medians": (I, [P, LL, I, I, I, I, P, P, P]),
     "medp_probe_moments": (I, [P, LL, I, P, P, P, LL, P, P, I, I, P]),
     "medp_probe_terms_ws_bytes": (SZ, [I, I, I, LL]),
     "medp_logistic_newton_terms": (I, [P, LL, I, P, I, P, P, P, LL, P, P, P, P, P, P, P, P, SZ, I, I, P]),

@@ -108,6 +108,26 @@ class LabelMetrics:
         return resampled_binary_metrics(self.y, probs.reshape(1, -1), self.idx, self.offsets, self.max_len)
 
 
+def column_medians(planes: torch.Tensor, take_abs: bool = False):
+    """planes [C, N] fp32 or int32 on the device (rows may be strided: a view `buf[:, :N]` of wider planes is read in place) ->
+    (median [C] fp64, n_valid [C] int32), device tensors, no synchronisation.  numpy's median of every row after `take_abs`, NaNs
+    dropped (`np.nanmedian`; a row without a valid entry: NaN): exact selection by radix (csrc/trajectory_audit.hip), any N up to
+    MEDP_COLUMN_MEDIAN_MAX_N, none of the 16384-row limit of the kernels that sort in LDS."""
+    if not isinstance(planes, torch.Tensor) or planes.dtype not in (torch.float32, torch.int32):
+        raise TypeError("column_medians reads fp32 or int32 planes")
+    if planes.ndim != 2 or planes.shape[0] < 1 or planes.shape[1] < 1:
+        raise ValueError("column_medians: planes [C >= 1, N >= 1]")
+    C, N = planes.shape
+    if planes.stride(1) != 1 or (C > 1 and planes.stride(0) < N):
+        planes = planes.contiguous()
+    ld = planes.stride(0) if C > 1 else max(planes.stride(0), N)
+    median = torch.empty(C, dtype=F64, device=planes.device)
+    n_valid = torch.empty(C, dtype=torch.int32, device=planes.device)
+    check(lib().medp_column_medians(ptr(planes), ld, C, N, int(planes.dtype == torch.int32), int(bool(take_abs)), ptr(median), ptr(n_valid),
+                                    stream()), "column_medians")
+    return median, n_valid
+
+
 def nan_mean(v: torch.Tensor) -> torch.Tensor:
     """Mean of the entries that are not NaN; NaN when there is none (a device scalar, no synchronisation)."""
     ok = ~torch.isnan(v)
