@@ -508,7 +508,8 @@ int medp_gru_bwd_dgi16(const float* dh, const float* gates, const float* hn, con
  *   One class only: AUROC = AUPRC = NaN, BCE finite.  An empty replicate, or one with an index outside [0, N): NaN, NaN, NaN.
  *   max_len = the longest replicate (the caller drew the indices); above MEDP_RESAMPLED_METRICS_MAX_LEN: rc < 0, no launch. */
 #define MEDP_OFFSET_LOGISTIC_MAX_G 8
-#define MEDP_RESAMPLED_METRICS_MAX_LEN 16384 /* 8-byte keys: 128 KiB of the CU's 160 KiB LDS, a power of two for the bitonic sort */
+#define MEDP_LDS_SORT_MAX_LEN 16384 /* the one bound of the kernels that sort in LDS (csrc/rank_lds.h): the two names below */
+#define MEDP_RESAMPLED_METRICS_MAX_LEN MEDP_LDS_SORT_MAX_LEN /* 8-byte keys: 128 KiB of the CU's 160 KiB LDS, a power of two for the bitonic sort */
 int medp_raw_traj_summary(const float* x, double* out, int B, int T, int V, int recent_hours, void* stream);
 size_t medp_offset_logistic_ws_bytes(int n, int F, int G);
 int medp_offset_logistic_valgrad(const double* X, long long ldx, const double* y, const double* offset, const double* W,
@@ -577,7 +578,7 @@ int medp_temporal_usage_summary(const float* fus, const float* ts, const float* 
  *   image / TS / fusion head (numpy's float32 > float64; a NaN or +inf threshold predicts False: `_binarize` :126-135).  Integer
  *   counts only (LDS histograms, integer atomics into the zeroed output): deterministic.  Everything `_analyze_pathology` and
  *   `_plot_venn` report is a function of these 16 integers.  Null pointers or non-positive sizes: rc < 0, no launch. */
-#define MEDP_YOUDEN_MAX_LEN 16384 /* 8-byte keys: 128 KiB of the CU's 160 KiB LDS, a power of two for the bitonic sort */
+#define MEDP_YOUDEN_MAX_LEN MEDP_LDS_SORT_MAX_LEN /* 8-byte keys: 128 KiB of the CU's 160 KiB LDS, a power of two for the bitonic sort */
 int medp_youden_thresholds(const float* scores, const float* y, const float* mask, double* thr, double* youden_j, int* counts, int H,
                            int N, int K, void* stream);
 int medp_complementarity_cells(const float* scores, const float* y, const float* mask, const double* thr, int* cells, int N, int K,

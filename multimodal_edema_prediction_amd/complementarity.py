@@ -28,10 +28,10 @@ import numpy as np
 import torch
 
 from .abi import check, lib, ptr, require_gpu, stream
-from .probe_stats import pearson
+from .probe_stats import METRICS_MAX_LEN, pearson
 
 HEADS = ("img", "ts", "fus")
-YOUDEN_MAX_LEN = 16384             # MEDP_YOUDEN_MAX_LEN: the known rows of one label the threshold kernel sorts in LDS
+YOUDEN_MAX_LEN = METRICS_MAX_LEN   # MEDP_YOUDEN_MAX_LEN: the known rows of one label the threshold kernel sorts in LDS (one bound)
 VENN_IDS = ("100", "010", "110", "001", "101", "011", "111")      # (image, TS, fusion) digits, the reference's `_plot_venn` order
 CELL_KEYS = ("ts_only_and_fus_ok", "ts_only_but_fus_lost_it", "image_only_and_fus_ok", "image_only_but_fus_lost_it",
              "both_wrong_but_fus_saved", "all_three_wrong", "both_correct_and_fus_ok", "both_correct_but_fus_broke_it")

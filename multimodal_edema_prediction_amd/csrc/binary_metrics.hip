@@ -2,14 +2,12 @@
 // lists; DESIGN.md "Raw-trajectory probe", "Conditional-information probe", "Linear-head probes"): the one metrics kernel of all the
 // analysis probes (probe_stats.py).  fp64 throughout.
 //
-//   resampled_metrics_kernel    one resampled replicate per workgroup: gather, clip, bitonic sort in LDS, then tie-aware (one
-//                               threshold per distinct score) ROC area and average precision.
-#include "common.h"
-#include "medp_hip.h"
+//   resampled_metrics_kernel    one resampled replicate per workgroup: gather, clip, sort in LDS, then tie-aware (one threshold
+//                               per distinct score) ROC area and average precision.  The sort, the owned ranges with their scan,
+//                               the tie search and the fixed-tree sum are rank_lds.h's; the key layout is this kernel's.
+#include "rank_lds.h"
 
 namespace {
-
-constexpr double kNaN = __builtin_nan("");
 
 constexpr int RM_THREADS = 1024;
 constexpr unsigned long long RM_LABEL = 1ull << 63, RM_SCORE = ~RM_LABEL;     // the clipped score is positive: its sign bit carries the label
@@ -20,18 +18,6 @@ struct RmScratch {
     int total_pos;
     int bad;
 };
-
-// fixed-tree sum over the workgroup (the same order on every run)
-__device__ double block_sum_tree_f64(double v, double* red, int tid) {
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int s = RM_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 __global__ __launch_bounds__(RM_THREADS) void resampled_metrics_kernel(const unsigned char* __restrict__ y, const double* __restrict__ p,
                                                                         const int* __restrict__ idx, const long long* __restrict__ offsets,
@@ -66,50 +52,23 @@ __global__ __launch_bounds__(RM_THREADS) void resampled_metrics_kernel(const uns
         }
         keys[j] = key;
     }
-    bce = block_sum_tree_f64(bce, sc.red, tid) / (double)L;
+    bce = block_sum_tree_f64<RM_THREADS>(bce, sc.red, tid) / (double)L;
     if (sc.bad) {                            // an index outside [0, N): no metric is defined
         if (tid < 3) o[tid] = kNaN;
         return;
     }
-    // bitonic sort, descending by score
-    for (int k = 2; k <= M; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < M / 2; t += RM_THREADS) {
-                const int a = ((t & ~(j - 1)) << 1) | (t & (j - 1)), b = a | j;
-                const unsigned long long ka = keys[a], kb = keys[b];
-                const bool desc = (a & k) == 0;
-                if (((ka & RM_SCORE) < (kb & RM_SCORE)) == desc) {
-                    keys[a] = kb;
-                    keys[b] = ka;
-                }
-            }
-            __syncthreads();
-        }
+    lds_sort_desc<RM_THREADS, RM_SCORE>(keys, M, tid);            // descending by score: the label bit takes no part
     // thread t owns positions [c0, c1); positives before c0 by an inclusive scan of the per-thread counts
-    const int C = M > RM_THREADS ? M / RM_THREADS : 1;
-    const int c0 = min(tid * C, L), c1 = min(c0 + C, L);
+    const auto [C, c0, c1] = owned_range<RM_THREADS>(M, L, tid);
     int cnt = 0;
     for (int j = c0; j < c1; ++j) cnt += (int)(keys[j] >> 63);
-    sc.scan[0][tid] = cnt;
-    __syncthreads();
-    int cur = 0;
-    for (int s = 1; s < RM_THREADS; s <<= 1) {
-        sc.scan[cur ^ 1][tid] = sc.scan[cur][tid] + (tid >= s ? sc.scan[cur][tid - s] : 0);
-        cur ^= 1;
-        __syncthreads();
-    }
-    const int* incl = sc.scan[cur];
+    const int* incl = block_inclusive_scan<RM_THREADS>(cnt, sc.scan, tid);
     const int tp0 = incl[tid] - cnt;                                     // positives in [0, c0)
     const int P = incl[RM_THREADS - 1], Nn = L - P;
     // positives before the tie group that is open at c0 (its first element may lie in an earlier thread's range)
     int tp_prev = tp0, fp_prev = c0 - tp0;
     if (c0 < c1 && c0 > 0 && ((keys[c0 - 1] ^ keys[c0]) & RM_SCORE) == 0) {
-        const unsigned long long target = keys[c0] & RM_SCORE;
-        int lo = 0, hi = c0;                                             // first position whose score is <= target (descending order)
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if ((keys[mid] & RM_SCORE) > target) lo = mid + 1; else hi = mid;
-        }
+        const int lo = first_at_most(keys, RM_SCORE, keys[c0] & RM_SCORE, 0, c0);
         const int owner = lo / C;
         int tp = owner > 0 ? incl[owner - 1] : 0;
         for (int j = owner * C; j < lo; ++j) tp += (int)(keys[j] >> 63);
@@ -130,8 +89,8 @@ __global__ __launch_bounds__(RM_THREADS) void resampled_metrics_kernel(const uns
             fp_prev = fp;
         }
     }
-    const double area = block_sum_tree_f64((double)area2, sc.red, tid);      // integers below 2^53: exact in any order
-    ap = block_sum_tree_f64(ap, sc.red, tid);
+    const double area = block_sum_tree_f64<RM_THREADS>((double)area2, sc.red, tid);      // integers below 2^53: exact in any order
+    ap = block_sum_tree_f64<RM_THREADS>(ap, sc.red, tid);
     if (tid == 0) {
         const bool both = P > 0 && Nn > 0;
         o[0] = bce;
@@ -152,12 +111,7 @@ extern "C" int medp_resampled_binary_metrics(const unsigned char* y, const doubl
     MEDP_CHECK_ARG(max_len >= 0, "resampled_binary_metrics: max_len %d < 0", max_len);
     MEDP_CHECK_ARG(max_len <= MEDP_RESAMPLED_METRICS_MAX_LEN, "resampled_binary_metrics: replicate length %d exceeds the in-LDS sort limit %d",
                    max_len, MEDP_RESAMPLED_METRICS_MAX_LEN);
-    int M = 2;
-    while (M < max_len) M <<= 1;
-    MEDP_ONCE_PER_DEVICE({
-        hipFuncSetAttribute((const void*)resampled_metrics_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            MEDP_RESAMPLED_METRICS_MAX_LEN * 8);
-    });
+    const int M = lds_sort_staged_len<resampled_metrics_kernel>(max_len);
     resampled_metrics_kernel<<<R, RM_THREADS, (size_t)M * 8, (hipStream_t)stream>>>(y, p, idx, offsets, out, N, Rp, M);
     MEDP_LAUNCH_CHECK("medp_resampled_binary_metrics");
     return 0;

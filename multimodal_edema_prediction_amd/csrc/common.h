@@ -16,6 +16,8 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define MEDP_WAVE 64
 
+constexpr double kNaN = __builtin_nan(""), kInf = __builtin_inf();      // the fp64 analysis kernels' "undefined" and "+inf threshold"
+
 // ---- error plumbing (C ABI: 0 ok, <0 invalid argument, >0 hipError_t) --------------------------
 void medp_set_error(const char* fmt, ...);
 #define MEDP_CHECK_ARG(cond, ...)            \

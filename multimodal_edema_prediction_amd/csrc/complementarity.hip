@@ -1,21 +1,19 @@
 // Modality complementarity (the reference's analysis/complementarity.py; DESIGN.md "Modality complementarity"): the operating point of
 // every (head, label) and the 3-way contingency counts of a split, on the logits `conditional_information_probe.gather` leaves on the device.
 //
-//   youden_kernel      one workgroup per (head, label): compact the known rows into LDS, bitonic sort descending, one ROC point per
+//   youden_kernel      one workgroup per (head, label): compact the known rows into LDS, sort descending, one ROC point per
 //                      distinct score, and the FIRST maximum of the fp64 expression tp / P - fp / N over the points sklearn's
-//                      roc_curve keeps (the (0, 0) start point at +inf, drop_intermediate's second-difference rule).
+//                      roc_curve keeps (the (0, 0) start point at +inf, drop_intermediate's second-difference rule).  The sort,
+//                      the owned ranges with their scan, the tie search and the score's image are rank_lds.h's (shared with
+//                      resampled_metrics_kernel); the key layout and the argmax tree are this kernel's.
 //   known_counts_kernel  known rows and known positives per label, for the length check of an N above the in-LDS sort limit.
 //   cells_kernel       per label the 16 counts of (y, img > thr, ts > thr, fus > thr) over the known rows; integers only.
 #include <climits>
 #include <vector>
 
-#include "common.h"
-#include "medp_hip.h"
+#include "rank_lds.h"
 
 namespace {
-
-constexpr double kNaN = __builtin_nan("");
-constexpr double kInf = __builtin_inf();
 
 constexpr int YD_THREADS = 1024;
 constexpr unsigned long long YD_SCORE = 0xffffffff00000000ull;        // high word: the score's image; low word: label, later the positive count
@@ -28,21 +26,7 @@ struct YdScratch {
 };
 
 // fp32 -> u32 with the order of the finite scores; -0.0 and +0.0 share one image (one tie group)
-__device__ __forceinline__ unsigned score_image(float s) {
-    const unsigned b = __float_as_uint(s == 0.0f ? 0.0f : s);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ float image_score(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
-
-// first position in [lo, hi) of the descending keys whose score image is <= target (hi when there is none)
-__device__ __forceinline__ int first_at_most(const unsigned long long* keys, unsigned target, int lo, int hi) {
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if ((unsigned)(keys[mid] >> 32) > target) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+__device__ __forceinline__ unsigned score_image(float s) { return f32_order_key(s == 0.0f ? 0.0f : s); }
 
 __global__ __launch_bounds__(YD_THREADS) void youden_kernel(const float* __restrict__ scores, const float* __restrict__ y,
                                                              const float* __restrict__ mask, double* __restrict__ thr,
@@ -81,34 +65,12 @@ __global__ __launch_bounds__(YD_THREADS) void youden_kernel(const float* __restr
         if (tid == 0) thr[out] = youden_j[out] = kNaN;
         return;
     }
-    // bitonic sort, descending by (score, label)
-    for (int kk = 2; kk <= M; kk <<= 1)
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < M / 2; t += YD_THREADS) {
-                const int a = ((t & ~(j - 1)) << 1) | (t & (j - 1)), b = a | j;
-                const unsigned long long ka = keys[a], kb = keys[b];
-                const bool desc = (a & kk) == 0;
-                if ((ka < kb) == desc) {
-                    keys[a] = kb;
-                    keys[b] = ka;
-                }
-            }
-            __syncthreads();
-        }
+    lds_sort_desc<YD_THREADS, ~0ull>(keys, M, tid);  // descending by (score, label): whole keys
     // thread t owns positions [c0, c1); the low word becomes the inclusive count of positives at its position
-    const int C = M > YD_THREADS ? M / YD_THREADS : 1;
-    const int c0 = min(tid * C, L), c1 = min(c0 + C, L);
+    const auto [C, c0, c1] = owned_range<YD_THREADS>(M, L, tid);
     int cnt = 0;
     for (int j = c0; j < c1; ++j) cnt += (int)(keys[j] & 1ull);
-    sc.scan[0][tid] = cnt;
-    __syncthreads();
-    int cur = 0;
-    for (int st = 1; st < YD_THREADS; st <<= 1) {
-        sc.scan[cur ^ 1][tid] = sc.scan[cur][tid] + (tid >= st ? sc.scan[cur][tid - st] : 0);
-        cur ^= 1;
-        __syncthreads();
-    }
-    int run = sc.scan[cur][tid] - cnt;
+    int run = block_inclusive_scan<YD_THREADS>(cnt, sc.scan, tid)[tid] - cnt;
     for (int j = c0; j < c1; ++j) {
         run += (int)(keys[j] & 1ull);
         keys[j] = (keys[j] & YD_SCORE) | (unsigned long long)run;
@@ -124,8 +86,9 @@ __global__ __launch_bounds__(YD_THREADS) void youden_kernel(const float* __restr
         if (!last && (unsigned)(keys[j + 1] >> 32) == hj) continue;
         const int tp = (int)(unsigned)keys[j], fp = j + 1 - tp;
         if (!last && hj != first) {                          // drop_intermediate: an interior point on a straight stretch of both counts
-            const int pe = first_at_most(keys, hj, 0, j) - 1;                                            // end of the previous group
-            const int ne = first_at_most(keys, (unsigned)(keys[j + 1] >> 32) - 1u, j + 1, L) - 1;        // end of the next group
+            const unsigned below_next = (unsigned)(keys[j + 1] >> 32) - 1u;
+            const int pe = first_at_most(keys, YD_SCORE, (unsigned long long)hj << 32, 0, j) - 1;                 // end of the previous group
+            const int ne = first_at_most(keys, YD_SCORE, (unsigned long long)below_next << 32, j + 1, L) - 1;     // end of the next group
             const int tp_p = (int)(unsigned)keys[pe], fp_p = pe + 1 - tp_p;
             const int tp_n = (int)(unsigned)keys[ne], fp_n = ne + 1 - tp_n;
             if (tp_p - 2 * tp + tp_n == 0 && fp_p - 2 * fp + fp_n == 0) continue;
@@ -153,7 +116,7 @@ __global__ __launch_bounds__(YD_THREADS) void youden_kernel(const float* __restr
     }
     if (tid == 0) {
         const int best = sc.best_i[0];
-        double t = best < 0 ? kInf : (double)image_score((unsigned)(keys[best] >> 32));
+        double t = best < 0 ? kInf : (double)f32_from_order_key((unsigned)(keys[best] >> 32));
         if (t == 0.0) t = (double)s[(size_t)sc.zero_row * K + k];      // its sign: that of the first known row holding a zero
         thr[out] = t;
         youden_j[out] = best < 0 ? 0.0 : sc.best_j[0];
@@ -229,11 +192,7 @@ extern "C" int medp_youden_thresholds(const float* scores, const float* y, const
     }
     MEDP_CHECK_ARG(max_len <= MEDP_YOUDEN_MAX_LEN, "youden_thresholds: %d known rows of one label exceed the in-LDS sort limit %d", max_len,
                    MEDP_YOUDEN_MAX_LEN);
-    int M = 2;
-    while (M < max_len) M <<= 1;
-    MEDP_ONCE_PER_DEVICE({
-        hipFuncSetAttribute((const void*)youden_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MEDP_YOUDEN_MAX_LEN * 8);
-    });
+    const int M = lds_sort_staged_len<youden_kernel>(max_len);
     youden_kernel<<<H * K, YD_THREADS, (size_t)M * 8, st>>>(scores, y, mask, thr, youden_j, counts, N, K, M);
     MEDP_LAUNCH_CHECK("medp_youden_thresholds");
     return 0;

@@ -20,7 +20,6 @@
 
 namespace {
 
-constexpr double kNaN = __builtin_nan("");
 constexpr int PT_THREADS = 256, PT_WAVES = PT_THREADS / 64;
 constexpr int PT_ROWS = 64;                       // rows of one problem per workgroup (valgrad, scores)
 constexpr int MO_SLICES = 16, MO_THREADS = 64 * MO_SLICES;

@@ -15,8 +15,6 @@
 
 namespace {
 
-constexpr double kNaN = __builtin_nan("");
-
 // ---------------------------------------------------------------------------------------------------------------------
 // (a) per-(window, variable) summaries
 // ---------------------------------------------------------------------------------------------------------------------

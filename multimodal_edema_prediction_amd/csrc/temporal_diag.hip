@@ -9,9 +9,9 @@
 //   temporal_usage_summary_kernel one workgroup per (condition, label): the fp32 sigmoid of the gathered logits, widened, in the
 //                                 label-major layout the metrics kernel reads; mean |dp|, Pearson correlation against the full
 //                                 condition (centred, two passes) and the normalised entropy of the full condition's attention.
-//                                 Every reduction is a fixed tree: two launches are bit-identical, no floating-point atomics.
-#include "common.h"
-#include "medp_hip.h"
+//                                 Every reduction is a fixed tree (rank_lds.h's, the metrics kernel's too): two launches are
+//                                 bit-identical, no floating-point atomics.
+#include "rank_lds.h"
 
 namespace {
 
@@ -110,7 +110,6 @@ __global__ __launch_bounds__(256) void counterfactual_feats_kernel(const CfParam
 
 // --------------------------------------------------------------------------------------------------------------------------------
 constexpr int TU_THREADS = 256;
-constexpr double kNaN = __builtin_nan("");
 
 // exp(x) in fp32 for |x| <= 50 by the algorithm of numpy's float32 `exp` loop (its SIMD kernel on x86 with FMA): round(x log2 e) by the
 // 1.5 * 2^23 trick, Cody-Waite reduction by ln 2 in two fp32 pieces, a degree-5 / degree-2 rational in fused multiply-adds, an IEEE
@@ -144,24 +143,6 @@ __device__ __forceinline__ float tu_prob(float z) {
     return 1.0f / s;
 }
 
-// fixed-tree sums of NV values per thread over the workgroup: the same order on every run; every thread gets the totals
-template <int NV>
-__device__ void tu_block_sums(double (&v)[NV], double (*red)[TU_THREADS], int tid) {
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NV; ++q) red[q][tid] = v[q];
-    __syncthreads();
-    for (int s = TU_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int q = 0; q < NV; ++q) red[q][tid] += red[q][tid + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < NV; ++q) v[q] = red[q][0];
-}
-
 __global__ __launch_bounds__(TU_THREADS) void temporal_usage_summary_kernel(const float* __restrict__ fus, const float* __restrict__ ts,
                                                                              const float* __restrict__ attn, double* __restrict__ prob,
                                                                              double* __restrict__ sens, double* __restrict__ entropy,
@@ -190,7 +171,7 @@ __global__ __launch_bounds__(TU_THREADS) void temporal_usage_summary_kernel(cons
         }
     }
     if (c > 0) {
-        tu_block_sums<4>(a, red, tid);
+        block_sum_tree_f64<TU_THREADS, 4>(a, red, tid);
         const double m0 = a[0] / (double)N, mc = a[1] / (double)N;
         // pass 2: centred second moments
         double m[3] = {0.0, 0.0, 0.0};
@@ -200,7 +181,7 @@ __global__ __launch_bounds__(TU_THREADS) void temporal_usage_summary_kernel(cons
             m[1] += dc * dc;
             m[2] += d0 * dc;
         }
-        tu_block_sums<3>(m, red, tid);
+        block_sum_tree_f64<TU_THREADS, 3>(m, red, tid);
         if (tid == 0) {
             double* o = sens + ((size_t)(c - 1) * K + k) * 3;
             o[0] = a[2] / (double)N;
@@ -223,7 +204,7 @@ __global__ __launch_bounds__(TU_THREADS) void temporal_usage_summary_kernel(cons
             }
             h[0] += e * inv_log_s;
         }
-        tu_block_sums<1>(h, red, tid);
+        block_sum_tree_f64<TU_THREADS, 1>(h, red, tid);
         if (tid == 0) entropy[k] = h[0] / (double)N;
     }
 }

@@ -7,15 +7,14 @@
 //                          are shuffle sums of the tile followed by ONE integer atomic per (row, figure) and workgroup.
 //   column_median_kernel   one workgroup per column: exact selection by radix (four 8-bit passes over order-preserving keys, histograms in
 //                          LDS with integer atomics), then the smallest key above the lower median where the upper one is not its equal.
-//                          No sort, nothing of the column is staged: any length up to MEDP_COLUMN_MEDIAN_MAX_N.
+//                          No sort, nothing of the column is staged: any length up to MEDP_COLUMN_MEDIAN_MAX_N.  The fp32 key and its
+//                          inverse are rank_lds.h's (the Youden kernel's score image); NaN rejection, |.| and the int32 keys are here.
 #include <climits>
 
-#include "common.h"
-#include "medp_hip.h"
+#include "rank_lds.h"
 
 namespace {
 
-constexpr double kNaN = __builtin_nan("");
 constexpr float kNaNf = __builtin_nanf("");
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -168,17 +167,16 @@ __device__ __forceinline__ bool column_key(const void* column, size_t i, unsigne
     float v = ((const float*)column)[i];
     if (v != v) return false;
     if (TAKE_ABS) v = fabsf(v);
-    const unsigned b = __float_as_uint(v);
-    key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    key = f32_order_key(v);
     return true;
 }
 
 template <bool IS_INT>
 __device__ __forceinline__ double key_value_sum(unsigned ka, unsigned kb) {
     if (IS_INT) return ((double)(int)(ka ^ 0x80000000u) + (double)(int)(kb ^ 0x80000000u)) / 2.0;
-    const float a = __uint_as_float((ka & 0x80000000u) ? (ka ^ 0x80000000u) : ~ka);
+    const float a = f32_from_order_key(ka);
     if (ka == kb) return (double)a;                      // numpy averages ONE element when the count is odd: no a + a overflow
-    const float b = __uint_as_float((kb & 0x80000000u) ? (kb ^ 0x80000000u) : ~kb);
+    const float b = f32_from_order_key(kb);
     return (double)((a + b) * 0.5f);
 }
 

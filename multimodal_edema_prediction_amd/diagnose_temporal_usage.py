@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from .abi import check, lib, ptr, require_gpu, stream
-from .probe_stats import F64, METRICS_MAX_LEN, LabelMetrics, draw_cluster_bootstrap_indices, resampled_binary_metrics, to_device, to_host
+from .probe_stats import F64, METRICS_MAX_LEN, LabelMetrics, draw_cluster_bootstrap_indices, paired_replicate_metrics, placement, to_host
 
 CONDITIONS = ("full", "patient_shuffle", "ts_shuffle", "time_reverse", "time_permute")
 BATCH_SEED_STRIDE = 10007           # the batch's generator: default_rng(seed + 10007 * batch_idx)
@@ -250,14 +250,8 @@ def cluster_bootstrap_delta(subject_ids, y, valid, p_full, p_ablated, metric: st
                          f"MEDP_RESAMPLED_METRICS_MAX_LEN = METRICS_MAX_LEN = {METRICS_MAX_LEN}")
     if idx.size == 0:
         return nothing
-    held = [a.device for a in (p_full, p_ablated) if isinstance(a, torch.Tensor) and a.is_cuda]
-    device = held[0] if held else torch.device("cuda") if device is None else device
-    put = lambda p: p.to(F64).reshape(1, -1) if isinstance(p, torch.Tensor) and p.is_cuda else to_device(p, np.float64, device)[None]  # noqa: E731
-    yd = to_device((to_host(y) > 0.5), np.uint8, device)
-    idx_d, off_d = torch.as_tensor(idx, device=device), torch.as_tensor(offsets, device=device)
-    m = [resampled_binary_metrics(yd, put(p), idx_d, off_d, max(longest, 1)) for p in (p_full, p_ablated)]      # both launches, then the copies
-    col = _METRIC_COLUMN[metric]
-    full, ablated = m[0].cpu().numpy()[:, col], m[1].cpu().numpy()[:, col]
+    full, ablated = (m[:, _METRIC_COLUMN[metric]]
+                     for m in paired_replicate_metrics(to_host(y) > 0.5, p_full, p_ablated, idx, offsets, max(longest, 1), device))
     both = np.isfinite(full) & np.isfinite(ablated)
     if not both.any():
         return nothing
@@ -270,9 +264,8 @@ def summarise(pred: dict, labels: Sequence[str], n_boot: int, seed: int) -> dict
     "entropy" [4] (None without a [N, K, S > 0] attention), "audit", "bootstrap" [5] (empty when n_boot <= 0).  `pred`: what
     `collect_predictions` returns (device tensors or host arrays)."""
     require_gpu()
-    held = [v.device for v in (pred["y"], pred["img"]) if isinstance(v, torch.Tensor) and v.is_cuda]
-    dev = held[0] if held else torch.device("cuda", torch.cuda.current_device())
-    f32 = lambda a: a.to(dev, torch.float32) if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float32), device=dev)  # noqa: E731
+    _, put = placement((pred["y"], pred["img"]))
+    f32 = lambda a: put(a, np.float32, torch.float32)  # noqa: E731
     fus = torch.stack([f32(pred["fus"][c]) for c in CONDITIONS])
     ts = torch.stack([f32(pred["ts"][c]) for c in CONDITIONS])
     img, y, mask = f32(pred["img"]), f32(pred["y"]), f32(pred["mask"])

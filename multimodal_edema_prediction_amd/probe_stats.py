@@ -12,7 +12,7 @@ import torch
 from .abi import check, lib, ptr, stream
 
 F64 = torch.float64
-METRICS_MAX_LEN = 16384        # MEDP_RESAMPLED_METRICS_MAX_LEN: the longest replicate one workgroup sorts in LDS
+METRICS_MAX_LEN = 16384        # MEDP_LDS_SORT_MAX_LEN (= MEDP_RESAMPLED_METRICS_MAX_LEN): the longest replicate one workgroup sorts in LDS
 
 
 def to_host(a) -> np.ndarray:
@@ -73,14 +73,29 @@ def resampled_binary_metrics(y, p, idx=None, offsets=None, max_len=None) -> torc
     return out
 
 
+def placement(args, device=None):
+    """-> (device, put): the device of the first of `args` that is on a GPU already, else `device`, else cuda; `put(a, host_t, dev_t)`
+    leaves a device tensor where it is (as dev_t) and copies anything else there through a host array of host_t."""
+    held = [a.device for a in args if isinstance(a, torch.Tensor) and a.is_cuda]
+    device = held[0] if held else torch.device("cuda") if device is None else device
+    return device, lambda a, host_t, dev_t: a.to(dev_t) if isinstance(a, torch.Tensor) and a.is_cuda else to_device(a, host_t, device)
+
+
 def binary_metrics(y, probability, device=None) -> Dict[str, float]:
     """The reference's `_safe_metrics` through the metrics kernel (one identity replicate).  `y`, `probability`: host arrays or device
     tensors; what is on the device already stays there, `device` places the rest."""
-    held = [a.device for a in (probability, y) if isinstance(a, torch.Tensor) and a.is_cuda]
-    device = held[0] if held else torch.device("cuda") if device is None else device
-    put = lambda a, host_t, dev_t: a.to(dev_t) if isinstance(a, torch.Tensor) and a.is_cuda else to_device(a, host_t, device)  # noqa: E731
+    _, put = placement((probability, y), device)
     m = resampled_binary_metrics(put(y, np.uint8, torch.uint8), put(probability, np.float64, F64)[None]).cpu().numpy()[0]
     return {"bce": float(m[0]), "auroc": float(m[1]), "auprc": float(m[2])}
+
+
+def paired_replicate_metrics(y, p_a, p_b, idx, offsets, max_len: int, device=None):
+    """Two probability vectors (host or device) scored on the same replicates idx[offsets[r] : offsets[r + 1]] (int32 / int64 [R+1], host
+    or device) -> two host [R, 3] arrays of BCE, AUROC, AUPRC: both launches of the metrics kernel, then the two copies."""
+    device, put = placement((p_a, p_b), device)
+    yd, idx_d, off_d = put(y, np.uint8, torch.uint8), torch.as_tensor(idx, device=device), torch.as_tensor(offsets, device=device)
+    m = [resampled_binary_metrics(yd, put(p, np.float64, F64).reshape(1, -1), idx_d, off_d, max_len) for p in (p_a, p_b)]
+    return m[0].cpu().numpy(), m[1].cpu().numpy()
 
 
 class LabelMetrics:
@@ -193,11 +208,7 @@ def paired_bootstrap_gains(y, base_probability, probe_probability, idx, offsets,
     int64 [R+1], host or device), two metrics launches; one-class replicates leave the AUROC / AUPRC lists only; no replicate: six NaN."""
     samples = {"bce_gain": np.zeros(0), "auroc_gain": np.zeros(0), "auprc_gain": np.zeros(0)}
     if len(offsets) > 1:
-        yd = to_device(y, np.uint8, device)
-        idx_d, off_d = torch.as_tensor(idx, device=device), torch.as_tensor(offsets, device=device)
-        m = [resampled_binary_metrics(yd, to_device(p, np.float64, device)[None], idx_d, off_d, max_len)
-             for p in (base_probability, probe_probability)]              # both launches, then the two copies
-        base, probe = m[0].cpu().numpy(), m[1].cpu().numpy()
+        base, probe = paired_replicate_metrics(y, base_probability, probe_probability, idx, offsets, max_len, device)
         both = ~np.isnan(base[:, 1])                                     # replicates with both classes present
         samples = {"bce_gain": base[:, 0] - probe[:, 0], "auroc_gain": (probe[:, 1] - base[:, 1])[both],
                    "auprc_gain": (probe[:, 2] - base[:, 2])[both]}

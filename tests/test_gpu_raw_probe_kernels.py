@@ -163,7 +163,7 @@ def test_resampled_binary_metrics_with_a_ragged_gather(quantised, per_replicate_
     assert np.array_equal(again.cpu().numpy(), got, equal_nan=True)
 
 
-@pytest.mark.parametrize("N,Rp", [(1000, 3), (65, 1), (2, 2)])
+@pytest.mark.parametrize("N,Rp", [(1000, 3), (65, 1), (2, 2), (1025, 1), (2049, 2)])   # the last two: L < M, 2 and 4 positions per thread
 def test_resampled_binary_metrics_identity(N, Rp):
     rng = np.random.default_rng(N)
     y = (rng.random(N) < 0.5).astype(np.uint8)
