@@ -5,10 +5,14 @@
 //   * the LDS-DMA stream never stops: from K-tile nkt-2 on it carries K-tiles 0 and 1 of the NEXT tile (all but the last A
 //     piece, which P1 of the next K-tile 0 issues as in the steady state) — the next K-loop starts two K-tiles deep;
 //   * the epilogue needs no K buffer: bias / GELU / bf16 pack happen on the accumulator layout, the transposition to whole
-//     128-B rows goes through a 16-row bf16 patch per wave behind the K buffers, the bias slice arrives by LDS-DMA;
+//     128-B rows goes through a 16-row bf16 patch per wave behind the K buffers, the bias slice arrives by LDS-DMA.  A FULL tile
+//     runs a straight line per activation with the patch chain software-pipelined (row block i+1 is packed while row block i's
+//     two patch reads are in flight; no bounds test), a clipped tile the serial chain with a test per store: 2.4 -> 1.6 us per
+//     tile for qkv, 5.8 -> 4.7 us for fc1 (profiles/r07_gemm_v7_epilogue.txt);
 //   * nothing waits for the output stores until P2 of the next K-tile 1 (vmcnt is in order: the wait that ends the epilogue is
-//     counted so that it stops just before the 16 stores of a full tile, and there is no register-returning load anywhere in the
-//     steady state whose wait the compiler would have to place).
+//     counted so that it stops just before the 16 stores of a full tile — both epilogue forms issue exactly 16 per wave, in the
+//     same row order — and there is no register-returning load anywhere in the steady state whose wait the compiler would have
+//     to place).
 // What it bought (tools/trace_gemm_v7.py): the tile walk itself ~2 % on qkv / fc1 and 24 % fewer L2 misses;
 // dispatch, first-tile latency and the store drain turned out NOT to be what a round of workgroups pays for — the K-loop is
 // bound by L2 -> LDS delivery (L2 channels 79 % busy).
@@ -20,6 +24,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "common.h"
 #include "gemm_tile256.h"
@@ -57,7 +62,7 @@ constexpr int NWG = 256;                                               // reside
 #endif
 
 // FOLD: the LayerNorm-fold CONSUMER epilogue (gemm_variants.h) — its own instantiation, so that the plain kernel's register
-// allocation (251 of 256 VGPRs, no spill) is untouched by it
+// allocation (238 of 256 VGPRs, no spill) is untouched by it; it keeps the serial epilogue for every tile
 template <int TAG, bool FOLD = false>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v7_kernel(const MedpGemmArgs p, unsigned* slot, unsigned long long* trace, const int MB, const int SN) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -80,31 +85,28 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v7_kernel(const MedpGemmA
 
     // ---- LDS-DMA staging: half-tile = 128 rows x 8 chunks; lane's two pieces are rows (tid>>3) and (tid>>3)+64 ------
     const int srow = tid >> 3, schunk = (tid & 7) ^ (srow & 7);       // source chunk for LDS position (tid & 7)
-    // Source state: EIGHT buffer descriptors in SGPRs, one per 64-row piece position of the tile the A / W stream currently reads
-    // from (A rows 0-63 .. 192-255, W rows 0-63 .. 192-255: base = the position's first row, num_records = its rows below M / N,
-    // at most 64, in bytes), rebuilt with scalar operations where the stream switches to the next tile near the end of a K-loop
-    // (nobody, i.e. no next tile: no records), and ONE loop-invariant byte offset per operand and lane; the K advance is the
-    // instruction's scalar offset.  A load section therefore holds no address arithmetic on the vector ALU (it used to build a
-    // 64-bit address and select the zero chunk per piece, ~15 VALU per section, issued beside the partner wave's prioritised
-    // MFMAs), and rows past M / N are dropped by the range check: gemm_tile256.h says why whatever LDS then holds is harmless.
+    // Source state: TWO buffer descriptors in SGPRs, one per operand, for the tile the A / W stream currently reads from (base = the
+    // tile's first row, num_records = the bytes of its rows below M / N, at most 256 rows), rebuilt with scalar operations where the
+    // stream switches to the next tile near the end of a K-loop (nobody, i.e. no next tile: no records), and ONE loop-invariant byte
+    // offset per operand and lane (row tid >> 3 of a 64-row piece).  Which piece and which K-tile is the instruction's scalar
+    // offset: q * 64 * ld * 2 + k0 * 2, wave-uniform, scalar ALU only.  A load section therefore holds no address arithmetic on
+    // the vector ALU (it used to build a 64-bit address and select the zero chunk per piece, ~15 VALU per section, issued beside the
+    // partner wave's prioritised MFMAs), and rows past M / N are dropped by the range check, in which the scalar offset takes part:
+    // gemm_tile256.h says why that is exact and why whatever LDS then holds is harmless.  (One descriptor per 64-row piece position,
+    // as gemm_bf16_v6.hip keeps them, is 32 SGPRs across the K-loop: the compiler then spilled 57 SGPRs to VGPR lanes around it.)
     const unsigned voff_a = ((unsigned)srow * (unsigned)p.lda + (unsigned)(schunk * 8)) * 2u;
     const unsigned voff_w = ((unsigned)srow * (unsigned)p.ldw + (unsigned)(schunk * 8)) * 2u;
-    medp_rsrc_t ra[4], rw[4];
+    const unsigned piece_a = (unsigned)p.lda * 128u, piece_w = (unsigned)p.ldw * 128u;       // 64 rows in bytes
+    medp_rsrc_t ra, rw;
     // (readfirstlane: the clamp of a wave-uniform value is still selected as one vector instruction (v_med3), and a descriptor word
     //  in a VGPR wraps every load that uses it in a loop over its distinct values)
     auto set_m = [&](int mm) {         // mm < 0: nobody
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int rows = mm < 0 ? 0 : min(64, max(0, p.M - mm - q * 64));
-            ra[q] = lds_dma_rsrc(A + (size_t)(mm < 0 ? 0 : mm + q * 64) * (size_t)p.lda, (unsigned)__builtin_amdgcn_readfirstlane(rows * p.lda * 2));
-        }
+        const int rows = mm < 0 ? 0 : min(BM, max(0, p.M - mm));
+        ra = lds_dma_rsrc(A + (size_t)(mm < 0 ? 0 : mm) * (size_t)p.lda, (unsigned)__builtin_amdgcn_readfirstlane(rows * p.lda) * 2u);
     };
     auto set_n = [&](int nn) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int rows = nn < 0 ? 0 : min(64, max(0, p.N - nn - q * 64));
-            rw[q] = lds_dma_rsrc(W + (size_t)(nn < 0 ? 0 : nn + q * 64) * (size_t)p.ldw, (unsigned)__builtin_amdgcn_readfirstlane(rows * p.ldw * 2));
-        }
+        const int rows = nn < 0 ? 0 : min(BN, max(0, p.N - nn));
+        rw = lds_dma_rsrc(W + (size_t)(nn < 0 ? 0 : nn) * (size_t)p.ldw, (unsigned)__builtin_amdgcn_readfirstlane(rows * p.ldw) * 2u);
     };
     set_m(m0);
     set_n(n0);
@@ -119,8 +121,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v7_kernel(const MedpGemmA
 #endif
         char* dst = piece_dst(smem, b, which, wave, j);
         const int q = (which & 1) * 2 + j;
-        if (which < 2) blds16(ra[q], voff_a, (unsigned)k0 * 2u, dst);      // (K % 128 == 0: no chunk lies past K)
-        else blds16(rw[q], voff_w, (unsigned)k0 * 2u, dst);
+        if (which < 2) blds16(ra, voff_a, (unsigned)q * piece_a + (unsigned)k0 * 2u, dst);      // (K % 128 == 0: no chunk lies past K)
+        else blds16(rw, voff_w, (unsigned)q * piece_w + (unsigned)k0 * 2u, dst);
     };
     auto stage_a = [&](int k0, int b, int j) { stage_piece(k0, b, 0, j); stage_piece(k0, b, 1, j); };
     auto stage_w = [&](int k0, int b, int h) { stage_piece(k0, b, 2 + h, 0); stage_piece(k0, b, 2 + h, 1); };
@@ -258,13 +260,17 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v7_kernel(const MedpGemmA
         stamp(0, ((long long)m0 << 32) | (unsigned)n0);
         rows_live[0] = m0 + wm * 128 < p.M;
         rows_live[1] = m0 + wm * 128 + 64 < p.M;
+        // (Zeroed here, with the matrix pipe idle, and not where the epilogue has finished with a row block.  Written there, the
+        //  compiler sees one zero value and still copies it into the 128 registers at this point; with 128 separately opaque
+        //  zeros every accumulator stays live through the epilogue, whose temporaries otherwise reuse the row blocks already
+        //  packed, and 170-220 VGPRs spill.)
         float z;                       // an opaque zero: a known-zero accumulator makes the compiler peel K-tile 0 (code x6, +30 VGPRs)
         asm volatile("v_mov_b32 %0, 0" : "=v"(z));
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){z, z, z, z};
-        if (first) read_w(smem, 0, fw0a);      // later tiles: read in P4 of the previous tile's last K-tile
+        if (first) read_w(smem, 0, fw0a);     // later tiles: read in P4 of the previous tile's last K-tile
         else stage_stats(m0);                  // (the first tile's were staged by the prologue)
         first = false;
         if (wm == 1) MEDP_BAR();       // group 1 runs one barrier behind (group 0 pays its extra barrier after the loop)
@@ -323,43 +329,99 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v7_kernel(const MedpGemmA
         typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
         typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
         const float inv_dim = consumer ? 1.0f / (float)fo.ln_dim : 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            float rstd = 1.f, mr = 0.f;
-            if constexpr (consumer) {          // the row's mean / rstd from its per-tile (sum, sum of squares), added in tile order
-                const float* sr = (const float*)(smem + STATBUF) + (wm * 128 + i * 16 + opaque(fr)) * fo.stats_tiles * 2;
-                float a1 = 0.f, a2 = 0.f;
-                for (int t = 0; t < fo.stats_tiles; ++t) {
-                    const float2 st = *(const float2*)(sr + 2 * t);
-                    a1 += st.x;
-                    a2 += st.y;
-                }
-                const float mean = a1 * inv_dim;
-                rstd = rsqrtf(fmaxf(a2 * inv_dim - mean * mean, 0.f) + fo.ln_eps);
-                mr = mean * rstd;
-            }
+        // FULL tiles of the plain kernel: one straight line per activation, no bounds test, and the patch chain software-pipelined.
+        // The serial form below pays, per row block, LDS write -> read latency + store issue with nothing to fill it (the memory
+        // clobbers hold block i+1's arithmetic behind block i's read).  Here block i+1 is computed and packed WHILE block i's two
+        // ds_read_b128 are in flight; they are the only LDS operations outstanding at that point (the bias slice was waited for by
+        // its first use, in block 0), so the wait the compiler places in front of the stores is exactly "those two reads".  Block
+        // i+1's patch writes follow block i's reads in program order, which is all the LDS needs (MEDP_WAVE_LDS_SYNC); the
+        // sched_barriers keep the compiler from moving the arithmetic back out of the shadow of the reads.  16 stores per wave, rows
+        // in the same order as below: the vmcnt(16) that ends the epilogue counts them.
+        auto pack_block = [&](int i, auto act, u32x2 (&pk)[4]) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                f32x4 v;
-                if constexpr (consumer) {      // (bias and column sums are re-read per element group: 32 registers less than holding them across i)
-                    const f32x4 cj = *(const f32x4*)(smem + CSBUF + bias_cur * 1024 + (wn * 64 + j * 16 + kq * 4) * 4);
-                    const f32x4 bb = *(const f32x4*)(smem + BIASBUF + bias_cur * 1024 + (wn * 64 + j * 16 + kq * 4) * 4);
-                    v = acc[i][j] * rstd - mr * cj + bb;
-                } else {
-                    v = acc[i][j] + bj[j];
-                }
-                if (p.act == 1) v = gelu_bf16_4(v);
-                *(u32x2*)(wl + fr * PROW + j * 32 + kq * 8) = (u32x2){pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
+                f32x4 v = acc[i][j] + bj[j];
+                if constexpr (decltype(act)::value) v = gelu_bf16_4(v);
+                pk[j] = (u32x2){pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
             }
-            MEDP_WAVE_LDS_SYNC();
+        };
+        auto epilogue_full = [&](auto act) {
+            char* cp = (char*)((bf16_t*)p.C + (size_t)(m0 + wm * 128 + prow) * p.ldc + ncol);
+            const size_t rows8 = (size_t)p.ldc * 16;                       // 8 rows of C in bytes
+            u32x2 pk[4];
+            u32x4 o[2];
+            auto through_patch = [&]() {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int row = h * 8 + prow;
-                const int m = m0 + wm * 128 + i * 16 + row;
-                const u32x4 o = *(const u32x4*)(wl + row * PROW + pchunk * 16);
-                if (m < p.M && ncol < p.N) __builtin_nontemporal_store(o, (u32x4*)((bf16_t*)p.C + (size_t)m * p.ldc + ncol));
+                for (int j = 0; j < 4; ++j) *(u32x2*)(wl + fr * PROW + j * 32 + kq * 8) = pk[j];
+                MEDP_WAVE_LDS_SYNC();
+#pragma unroll
+                for (int h = 0; h < 2; ++h) o[h] = *(const u32x4*)(wl + (h * 8 + prow) * PROW + pchunk * 16);
+                MEDP_WAVE_LDS_SYNC();
+            };
+            pack_block(0, act, pk);
+            through_patch();
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (i + 1 < 8) pack_block(i + 1, act, pk);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    __builtin_nontemporal_store(o[h], (u32x4*)cp);
+                    cp += rows8;
+                }
+                if (i + 1 < 8) through_patch();
             }
-            MEDP_WAVE_LDS_SYNC();
+        };
+        // clipped tiles (and the LayerNorm-fold consumer): one row block after the other, every store tested
+        const bool pipelined = !FOLD && full_tile;
+        if constexpr (!FOLD) {
+            if (full_tile) {
+                if (p.act == 1) epilogue_full(std::true_type{});
+                else epilogue_full(std::false_type{});
+            }
+        }
+        // clipped tiles (and the LayerNorm-fold consumer): one row block after the other, every store tested.  (Written in place:
+        // as a lambda beside epilogue_full the same text allocates 252 / 256 VGPRs instead of 237 / 241.)
+        if (!pipelined) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                float rstd = 1.f, mr = 0.f;
+                if constexpr (consumer) {          // the row's mean / rstd from its per-tile (sum, sum of squares), added in tile order
+                    const float* sr = (const float*)(smem + STATBUF) + (wm * 128 + i * 16 + opaque(fr)) * fo.stats_tiles * 2;
+                    float a1 = 0.f, a2 = 0.f;
+                    for (int t = 0; t < fo.stats_tiles; ++t) {
+                        const float2 st = *(const float2*)(sr + 2 * t);
+                        a1 += st.x;
+                        a2 += st.y;
+                    }
+                    const float mean = a1 * inv_dim;
+                    rstd = rsqrtf(fmaxf(a2 * inv_dim - mean * mean, 0.f) + fo.ln_eps);
+                    mr = mean * rstd;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    f32x4 v;
+                    if constexpr (consumer) {      // (bias and column sums are re-read per element group: 32 registers less than holding them across i)
+                        const f32x4 cj = *(const f32x4*)(smem + CSBUF + bias_cur * 1024 + (wn * 64 + j * 16 + kq * 4) * 4);
+                        const f32x4 bb = *(const f32x4*)(smem + BIASBUF + bias_cur * 1024 + (wn * 64 + j * 16 + kq * 4) * 4);
+                        v = acc[i][j] * rstd - mr * cj + bb;
+                    } else {
+                        v = acc[i][j] + bj[j];
+                    }
+                    if (p.act == 1) v = gelu_bf16_4(v);
+                    *(u32x2*)(wl + fr * PROW + j * 32 + kq * 8) = (u32x2){pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
+                }
+                MEDP_WAVE_LDS_SYNC();
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int row = h * 8 + prow;
+                    const int m = m0 + wm * 128 + i * 16 + row;
+                    const u32x4 o = *(const u32x4*)(wl + row * PROW + pchunk * 16);
+                    if (m < p.M && ncol < p.N) __builtin_nontemporal_store(o, (u32x4*)((bf16_t*)p.C + (size_t)m * p.ldc + ncol));
+                }
+                MEDP_WAVE_LDS_SYNC();
+            }
         }
         // K-tiles 0 and 1 of the next tile (and the ticket) have landed once everything older than the 16 output stores of a
         // full tile has; a clipped tile issues an unknown number of stores and waits for all of them
@@ -465,7 +527,7 @@ int launch_v7(const MedpGemmArgs& a, hipStream_t stream) {
 bool medp_gemm_v7_supports(const MedpGemmArgs& a) {
     return a.out_bf16 && a.residual == nullptr && a.scale == nullptr && a.N % 8 == 0 && a.ldc % 8 == 0 &&
            a.K % 128 == 0 && a.K >= 256 && (long long)a.M * a.lda < (1ll << 31) && (long long)a.N * a.ldw < (1ll << 31) &&
-           a.lda < (1 << 24) && a.ldw < (1 << 24);       // (64 rows of a piece within a descriptor's 32-bit num_records)
+           a.lda < (1 << 23) && a.ldw < (1 << 23);       // (the 256 rows of a tile within a descriptor's 32-bit offsets and num_records)
 }
 
 bool medp_gemm_v7_eligible(const MedpGemmArgs& a) {

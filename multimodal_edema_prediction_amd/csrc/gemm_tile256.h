@@ -33,25 +33,34 @@
 // A rows 64-127 of K-tile 0, then A rows 0-63, W half 0, W half 1 of K-tile 1 (its A rows 64-127 follow in P1 of K-tile 0) —
 // so the counts hold from the first K-tile on.
 //
-// ADDRESSING of the A / W stream: buffer-addressed LDS-DMA (blds16 in common.h, `buffer_load_dwordx4 ... offen lds`).  Every 64-row
-// piece position of a tile (A rows 0-63 .. 192-255, W likewise) has its own descriptor in SGPRs — base = the position's first
-// row, num_records = the bytes of its rows below M / N (at most 64 rows; none where the stream has no next tile) — built with
-// scalar operations once per tile; a lane's vector offset (srow * ld + schunk * 8) * 2 is loop-invariant, one VGPR per operand; the
-// K advance is the instruction's scalar offset.  A steady-state load section is then ds_reads, two m0 writes and two loads:
-// no vector instruction computes an address (the per-lane 64-bit address and the select of a zero chunk were ~15 VALU per
-// section, issued at priority 0 beside the partner wave's 16 prioritised MFMAs: profiles/r05_gemm_buffer_dma.txt).  The buffer
-// form counts in vmcnt exactly like the flat one, dropped lanes included: the hand-counted waits above are unchanged.
+// ADDRESSING of the A / W stream: buffer-addressed LDS-DMA (blds16 in common.h, `buffer_load_dwordx4 ... offen lds`).  The descriptors
+// live in SGPRs and are built with scalar operations once per tile; a lane's vector offset (srow * ld + schunk * 8) * 2 is
+// loop-invariant, one VGPR per operand; what moves is the instruction's scalar offset.  A steady-state load section is then ds_reads,
+// two m0 writes and two loads: no vector instruction computes an address (the per-lane 64-bit address and the select of a zero chunk
+// were ~15 VALU per section, issued at priority 0 beside the partner wave's 16 prioritised MFMAs: profiles/r05_gemm_buffer_dma.txt).
+// The buffer form counts in vmcnt exactly like the flat one, dropped lanes included: the hand-counted waits above are unchanged.
+//   * gemm_bf16_v6.hip: one descriptor per 64-row piece position of the tile (A rows 0-63 .. 192-255, W likewise): base = the
+//     position's first row, num_records = the bytes of its rows below M / N (at most 64 rows); the scalar offset carries the K
+//     advance only.
+//   * gemm_bf16_v7.hip: ONE descriptor per operand: base = the tile's first row, num_records = the bytes of its rows below M / N (at
+//     most 256 rows; none where the stream has no next tile); the scalar offset is q * 64 * ld * 2 + k0 * 2 for piece position q.
+//     (Eight descriptors are 32 SGPRs held across the K-loop; around it the compiler spilled 57 SGPRs to VGPR lanes.)
 // What the range check is relied on for (tools/probe_buffer_lds.hip measured both on gfx950):
 //   * the scalar offset TAKES PART in the check (each dword of a lane is dropped iff vector + scalar offset of that dword is
-//     >= num_records), and the design holds either way: all row and tile movement is in the descriptors' bases, the scalar offset
-//     carries only the K advance, and that never leaves a row (k0 + 64 <= K <= ld), so the last live row's chunk still ends at or
-//     below num_records = rows * ld * 2 while the first dead row starts at it;
+//     >= num_records).  v6 holds either way: all row and tile movement is in the descriptors' bases, the scalar offset never leaves a
+//     row (k0 + 64 <= K <= ld), so the last live row's chunk still ends at or below num_records = rows * ld * 2 while the first dead
+//     row starts at it.  v7 DEPENDS on it: a lane of piece q addresses byte ((q * 64 + srow) * ld + k0 + schunk * 8) * 2 of the tile,
+//     row r = q * 64 + srow, and since k0 + schunk * 8 + 8 <= K <= ld all 16 bytes lie in [r * ld * 2, (r + 1) * ld * 2): below
+//     num_records = rows * ld * 2 iff r < rows, whole chunks either way.  The sum stays below 2^32 (256 * ld * 2 with ld < 2^23,
+//     medp_gemm_v7_supports), so it cannot wrap back into range.  Without the scalar offset in the check, rows past M / N of a tile
+//     would be READ (up to 255 rows past the operand's end) — the results would still be right, by the next point, the reads not;
 //   * a lane past num_records reads nothing and writes ZEROS to LDS, as the zero chunk did — but nothing depends on it: a row of
 //     A at or past M only ever feeds output rows >= M, a row of W at or past N only output columns >= N, and neither is stored
-//     (every epilogue tests m < M and n < N per element; the LayerNorm-fold producer adds only stored elements into its row sums and
-//     writes zeros for the rows between M and the next multiple of 256; the consumer reads row statistics, not LDS rows).  Rows
-//     112-127 of a group's A half under 224-row tiles lie past their descriptor (48 rows) and are skipped at compile time by
-//     read_a / mma.  Whatever such LDS rows hold — zeros or a previous K-tile — cannot reach a stored element.
+//     (every epilogue tests m < M and n < N per element, or runs on a tile that lies wholly below M and N; the LayerNorm-fold producer
+//     adds only stored elements into its row sums and writes zeros for the rows between M and the next multiple of 256; the consumer
+//     reads row statistics, not LDS rows).  Rows 112-127 of a group's A half under 224-row tiles lie past their descriptor (48 rows)
+//     and are skipped at compile time by read_a / mma.  Whatever such LDS rows hold — zeros or a previous K-tile — cannot reach a
+//     stored element.
 // The one-tile kernel keeps the per-lane form for K % 64 != 0 (chunks past K INSIDE a K-tile need a select per lane); the bias,
 // column-sum and row-statistics side streams stay on glds16.
 #pragma once

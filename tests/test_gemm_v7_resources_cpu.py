@@ -1,0 +1,50 @@
+"""Register resources of the persistent block GEMM (csrc/gemm_bf16_v7.hip), read from the kernel metadata of its gfx950 code object
+(the amdhsa.kernels note: counts only, no instruction text).  The plain kernel <TAG, false> keeps every value in registers — its
+`s_waitcnt vmcnt(N)` waits are counted by hand, a scratch access would shift them — and, with one buffer descriptor per operand
+instead of four, spills 35 SGPRs to VGPR lanes where it spilled 57 with eight descriptors held across the K-loop (none of the 35 inside
+the K-loop: tools/count_epilogue_insts.py lists the v_readlane / v_writelane of the K-loop and of the epilogue)."""
+import os
+import re
+import subprocess
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "multimodal_edema_prediction_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+READELF = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(HIPCC))), "llvm", "bin", "llvm-readelf")
+
+SGPR_SPILLS_PLAIN = 35          # eight descriptors: 57.  A lower figure is welcome: lower this constant with it.
+
+
+def _kernel_metadata(src: str, tmp: str) -> dict:
+    """mangled kernel name -> {field: int} from the code object's metadata note"""
+    obj = os.path.join(tmp, src + ".co")
+    cmd = [HIPCC, "--offload-arch=gfx950", "--offload-device-only", "--no-gpu-bundle-output", "-O3", "-std=c++17", "-x", "hip", "-I", CSRC,
+           "-I", os.path.join(ROOT, "include"), "-Wno-unused-result", "-Wno-unused-value", "-c", os.path.join(CSRC, src), "-o", obj]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:]
+    notes = subprocess.run([READELF, "--notes", obj], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert notes.returncode == 0, notes.stdout[-2000:]
+    kernels = {}
+    for block in re.split(r"\n\s+- \.agpr_count:", notes.stdout)[1:]:        # one list entry of amdhsa.kernels each (.agpr_count sorts first)
+        name = re.search(r"^\s+\.name:\s+(\S+)$", block, re.M)
+        fields = {k: int(v) for k, v in re.findall(r"^\s+\.(vgpr_count|sgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\d+)$", block, re.M)}
+        if name and fields:
+            kernels[name.group(1)] = fields
+    return kernels
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC) or not os.path.exists(READELF), reason="needs hipcc and llvm-readelf")
+def test_plain_persistent_kernel_resources():
+    with tempfile.TemporaryDirectory() as tmp:
+        kernels = _kernel_metadata("gemm_bf16_v7.hip", tmp)
+    plain = {k: v for k, v in kernels.items() if re.search(r"gemm_bf16_nt_v7_kernelILi\d+ELb0E", k)}
+    assert len(plain) == 2, f"expected the two plain instantiations, found {sorted(kernels)} (metadata format changed?)"
+    for k, v in plain.items():
+        assert set(v) == {"vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size"}, (k, v)
+        assert v["private_segment_fixed_size"] == 0, f"{k} uses scratch: {v}"
+        assert v["vgpr_spill_count"] == 0, f"{k} spills VGPRs: {v}"
+        assert v["vgpr_count"] <= 256, f"{k}: {v}"
+        assert v["sgpr_spill_count"] == SGPR_SPILLS_PLAIN, f"{k}: {v['sgpr_spill_count']} SGPRs spilled, expected {SGPR_SPILLS_PLAIN}"
