@@ -15,13 +15,14 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MEDP_HIP_LIB") or os.path.join(_HERE, "libmedp_hip.so")   # override: the -DMEDP_V7_PHASE_TRACE profiling build
 
+ABI_VERSION = 4      # medp_version() of the library these struct layouts belong to (csrc/api.cpp)
+
 P, I, F, U, LL, SZ = c_void_p, c_int, c_float, c_uint, c_longlong, c_size_t
 
 
 class MedpVitLayer(ctypes.Structure):
     _fields_ = [(n, P) for n in ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ls1", "ln2_w", "ln2_b",
-                                 "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2",
-                                 "qkv_wg", "fc1_wg", "qkv_cs", "qkv_b2", "fc1_cs", "fc1_b2")]      # LayerNorm fold (include/medp_hip.h)
+                                 "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2")]
 
 
 class MedpVitWeights(ctypes.Structure):
@@ -233,6 +234,11 @@ def lib() -> ctypes.CDLL:
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
+        built = L.medp_version()
+        if built != ABI_VERSION:      # another layout of the weight structs: its kernels would walk them at the wrong stride
+            raise RuntimeError(
+                f"{LIB_PATH} has ABI version {built}, this package expects {ABI_VERSION}: rebuild it with "
+                "`python -m multimodal_edema_prediction_amd.build --force` (`--trace` / `--ablate` for the variant libraries).")
         _lib = L
     return _lib
 

@@ -14,7 +14,7 @@ void medp_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* medp_last_error(void) { return g_err; }
-extern "C" int medp_version(void) { return 3; }      // 2: MedpVitLayer carries the LayerNorm-fold operands; 3: MedpDuettWeights without the five emb_* fields of the retired psi kernel
+extern "C" int medp_version(void) { return 4; }      // 2: MedpVitLayer carries the LayerNorm-fold operands; 3: MedpDuettWeights without the five emb_* fields of the retired psi kernel; 4: MedpVitLayer without the LayerNorm-fold operands
 extern "C" const char* medp_arch(void) { return "gfx950"; }
 
 // ---- RNG epoch (see common.h) and a one-word device counter ------------------------------------------------------------

@@ -20,10 +20,6 @@ int gemm_check_args(const MedpGemmArgs& a, const char* who) {
     MEDP_CHECK_ARG(((uintptr_t)a.A & 15) == 0 && ((uintptr_t)a.W & 15) == 0 && ((uintptr_t)a.C & 15) == 0,
                    "%s: operands must be 16-byte aligned", who);
     MEDP_CHECK_ARG(a.act == 0 || a.act == 1, "%s: act must be 0 (none) or 1 (gelu)", who);
-    const MedpGemmFold& f = a.fold;
-    MEDP_CHECK_ARG(!f.stats_in || (f.colsum && f.ln_dim > 0 && f.stats_tiles > 0 && f.stats_tiles <= 4 && a.out_bf16 && !a.residual && !a.scale),
-                   "gemm(fold): a consumer needs colsum, ln_dim, 1..4 stats tiles, a bf16 result and no residual / scale");
-    MEDP_CHECK_ARG(!f.c2 || (f.stats_out && !a.out_bf16 && f.ldc2 % 4 == 0), "gemm(fold): a producer writes fp32 C, c2 (ld % 4 == 0) and stats_out");
     return 0;
 }
 
@@ -33,7 +29,6 @@ struct GemmPlan {
     int kernel;
     int nsplit;          // K slices (> 1: split-K through the workspace; 128-row tiles only)
     bool ragged_rows;    // v7 only: the rows past the last full 256-row tile go to a skinny launch of their own
-    bool fold_ok;        // the shape may carry the LayerNorm fold (it takes the 256-tile kernels on whole tiles)
 };
 
 // Every dispatch rule, in the order in which it fires.  Pure: reads the shape, the epilogue operands' presence and the switches.
@@ -44,10 +39,10 @@ GemmPlan gemm_plan(const MedpGemmArgs& a, int tag, bool has_workspace) {
     static const int v7_on = medp_env_int("MEDP_GEMM_V7", 1);
     static const int ragged_on = medp_env_int("MEDP_GEMM_RAGGED", 0);
     const int M = a.M, N = a.N, K = a.K;
-    // the 256 x 256 tiles (one workgroup per CU) once they occupy most of the chip; the only kernels that carry the LayerNorm fold
+    // the 256 x 256 tiles (one workgroup per CU) once they occupy most of the chip
     const int tiles256 = ((M + 255) / 256) * ((N + 255) / 256);
     const bool tile256 = M >= 2048 && N >= 256 && (variant == 6 || (variant == 0 && tiles256 >= 160));
-    GemmPlan pl{GEMM_T128x128, 1, false, tile256 && !ragged_on && K % 64 == 0 && N % 256 == 0};
+    GemmPlan pl{GEMM_T128x128, 1, false};
 
     // Split-K for SMALL grids (DuETT's skinny GEMMs: 25-100 tiles on 256 CUs): S slices so that tiles x S fills the chip.  Only with
     // a workspace, never for the tagged launches; tiles as the 128-row kernel cuts them; a split pays at 64-127 tiles only for a long K.
@@ -115,7 +110,7 @@ int gemm_launch(const MedpGemmArgs& a, const GemmPlan& pl, int tag, float* works
 
 // a dense operand-less GEMM of this shape, for the questions that only the plan answers
 MedpGemmArgs gemm_shape(int M, int N, int K) {
-    return MedpGemmArgs{nullptr, nullptr, nullptr, M, N, K, K, K, N, nullptr, nullptr, nullptr, N, 0, 0, nullptr, 0, MedpGemmFold{}};
+    return MedpGemmArgs{nullptr, nullptr, nullptr, M, N, K, K, K, N, nullptr, nullptr, nullptr, N, 0, 0, nullptr, 0};
 }
 
 }  // namespace
@@ -123,8 +118,6 @@ MedpGemmArgs gemm_shape(int M, int N, int K) {
 int medp_gemm_run(const MedpGemmArgs& args, int tag, float* workspace, size_t workspace_bytes, void* stream) {
     MEDP_TRY(gemm_check_args(args, "gemm"));
     const GemmPlan pl = gemm_plan(args, tag, workspace != nullptr);
-    MEDP_CHECK_ARG(!(args.fold.c2 || args.fold.stats_in) || pl.fold_ok, "gemm(fold): M=%d N=%d K=%d does not take the 256-tile kernels",
-                   args.M, args.N, args.K);
     MEDP_CHECK_ARG(pl.nsplit == 1 || workspace_bytes >= (size_t)pl.nsplit * args.M * args.N * sizeof(float),
                    "gemm: split-K workspace too small (medp_gemm_nt_workspace_bytes)");
     MedpGemmArgs a = args;
@@ -139,10 +132,6 @@ int medp_gemm_run(const MedpGemmArgs& args, int tag, float* workspace, size_t wo
     return rc;
 }
 
-bool medp_gemm_fold_eligible(int M, int N, int K) {
-    return gemm_plan(gemm_shape(M, N, K), 1, false).fold_ok;
-}
-
 extern "C" size_t medp_gemm_nt_workspace_bytes(int M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
     const int S = gemm_plan(gemm_shape(M, N, K), 0, true).nsplit;
@@ -152,14 +141,14 @@ extern "C" size_t medp_gemm_nt_workspace_bytes(int M, int N, int K) {
 extern "C" int medp_gemm_bf16_nt(const void* A, const void* W, void* C, int M, int N, int K, int lda, int ldw, int ldc,
                                  const float* bias, const float* scale, const float* residual, int ldr, int act, int out_bf16,
                                  void* stream) {
-    const MedpGemmArgs a{A, W, C, M, N, K, lda, ldw, ldc, bias, scale, residual, ldr, act, out_bf16, nullptr, 0, MedpGemmFold{}};
+    const MedpGemmArgs a{A, W, C, M, N, K, lda, ldw, ldc, bias, scale, residual, ldr, act, out_bf16, nullptr, 0};
     return medp_gemm_run(a, 0, nullptr, 0, stream);
 }
 
 extern "C" int medp_gemm_bf16_nt_ws(const void* A, const void* W, void* C, int M, int N, int K, int lda, int ldw, int ldc,
                                     const float* bias, const float* scale, const float* residual, int ldr, int act, int out_bf16,
                                     float* workspace, size_t workspace_bytes, void* stream) {
-    const MedpGemmArgs a{A, W, C, M, N, K, lda, ldw, ldc, bias, scale, residual, ldr, act, out_bf16, nullptr, 0, MedpGemmFold{}};
+    const MedpGemmArgs a{A, W, C, M, N, K, lda, ldw, ldc, bias, scale, residual, ldr, act, out_bf16, nullptr, 0};
     return medp_gemm_run(a, 0, workspace, workspace_bytes, stream);
 }
 
@@ -171,7 +160,7 @@ extern "C" int medp_dbg_gemm_tile256(int kernel, const void* A, const void* W, v
                                      const float* bias, const float* scale, const float* residual, int ldr, int act, int out_bf16,
                                      void* stream) {
     MEDP_CHECK_ARG(kernel == 6 || kernel == 7, "gemm_tile256: kernel must be 6 or 7");
-    const MedpGemmArgs a{A, W, C, M, N, K, lda, ldw, ldc, bias, scale, residual, ldr, act, out_bf16, nullptr, 0, MedpGemmFold{}};
+    const MedpGemmArgs a{A, W, C, M, N, K, lda, ldw, ldc, bias, scale, residual, ldr, act, out_bf16, nullptr, 0};
     MEDP_TRY(gemm_check_args(a, "gemm_tile256"));
     if (kernel == 6) return medp_gemm_v6_launch(a, 0, stream);
     MEDP_CHECK_ARG(medp_gemm_v7_supports(a), "gemm_tile256: the persistent kernel needs a bf16 result, no residual / scale, K %% 128 == 0, K >= 256");
@@ -182,19 +171,16 @@ extern "C" int medp_dbg_gemm_tile256(int kernel, const void* A, const void* W, v
 
 // Debug hook (NOT part of the C ABI in include/medp_hip.h; tests/test_gemm_plan_cpu.py): the plan of a shape, out[0] = kernel family
 // (64: 128 x 64 tiles, 128: 128 x 128 tiles, 3 / 6 / 7: v3 / v6 / v7), out[1] = K slices, out[2] = ragged rows as their own launch.
-// Leading dimensions are K, K, N; fold 0 / 1 / 2 = none / producer / consumer.  Touches no device.
+// Leading dimensions are K, K, N.  Touches no device.
 extern "C" int medp_dbg_gemm_plan(int tag, int M, int N, int K, int has_workspace, int has_residual, int has_scale, int out_bf16,
-                                  int fold, int* out) {
-    MEDP_CHECK_ARG(out && M > 0 && N > 0 && K > 0 && fold >= 0 && fold <= 2, "gemm_plan: bad argument");
+                                  int* out) {
+    MEDP_CHECK_ARG(out && M > 0 && N > 0 && K > 0, "gemm_plan: bad argument");
     static float present;                       // stands for an operand that is there; the plan never reads through it
     MedpGemmArgs a = gemm_shape(M, N, K);
     a.scale = has_scale ? &present : nullptr;
     a.residual = has_residual ? &present : nullptr;
     a.out_bf16 = out_bf16;
-    if (fold == 1) a.fold.c2 = &present;
-    if (fold == 2) a.fold.stats_in = &present;
     const GemmPlan pl = gemm_plan(a, tag, has_workspace != 0);
-    MEDP_CHECK_ARG(fold == 0 || pl.fold_ok, "gemm(fold): M=%d N=%d K=%d does not take the 256-tile kernels", M, N, K);
     out[0] = pl.kernel;
     out[1] = pl.nsplit;
     out[2] = pl.ragged_rows;

@@ -1,5 +1,5 @@
 // v6: the 256 x 256 x 64 ping-pong K-loop of gemm_tile256.h (tile map, phase plan and counted waits are described there), ONE tile
-// per workgroup, for every epilogue: bias / GELU / LayerScale / fp32 residual, fp32 or bf16 result, both sides of the LayerNorm fold.
+// per workgroup, for every epilogue: bias / GELU / LayerScale / fp32 residual, fp32 or bf16 result.
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "gemm_tile256.h"
@@ -8,8 +8,7 @@
 namespace {
 
 constexpr int LDS_MAIN = 2 * KBUF, LDS_EPI = 8 * 64 * 68 * 4;
-constexpr int LDS_STATS = LDS_EPI;                         // LayerNorm-fold producer: [256 rows][4 column waves][2] floats behind the epilogue patches
-constexpr int LDS_BYTES = LDS_STATS + 256 * 4 * 2 * 4;
+constexpr int LDS_BYTES = LDS_EPI > LDS_MAIN ? LDS_EPI : LDS_MAIN;
 static_assert(LDS_BYTES >= LDS_MAIN && LDS_BYTES <= 160 * 1024, "v6 LDS plan");
 
 // GR = tile rows per ping-pong group: 128 (256 x 256 tiles) or 112 (224 x 256 tiles for the N = 768 launches, see launch_v6).
@@ -19,7 +18,7 @@ static_assert(LDS_BYTES >= LDS_MAIN && LDS_BYTES <= 160 * 1024, "v6 LDS plan");
 // BUF: the A / W stream goes through buffer descriptors (K % 64 == 0, see launch_v6_gr); without it every lane builds its
 // own address and selects the zero chunk for what lies past M, N or K.  Same pieces in the same order either way.
 template <int TAG, int GR, bool BUF>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmArgs p, unsigned* slot) {
+__global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmArgs p) {
     static_assert(GR == 128 || GR == 112, "v6 group rows");
     constexpr int BM = 2 * GR;
     constexpr int NI1 = (GR - 64) / 16;                // 16-row blocks of the wave's second 64-row quadrant (a = 1)
@@ -34,31 +33,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
     MEDP_PROF_ENTER(p.prof, p.prof_flags);
 
     const Tile256Map map(p.M, p.N, BM);
-    const int tiles_n = map.tiles_n;
-    // Tile index.  Static: workgroup b owns tile b.  With a ticket block (`slot`, one-round grids inside a multi-stream step: proj /
-    // fc2, 195 tiles) MORE workgroups than tiles are launched and each draws its tile from the queue of its XCD (ticket t of XCD x
-    // is tile 8 t + x: the tile the static map gives that XCD's t-th workgroup, so the L2 locality of the map below holds): the
-    // tiles go to whichever CUs are free FIRST, a workgroup that becomes resident late — its CU still held short kernels of the
-    // step's other branch — finds the queue empty and leaves, instead of starting its 30-us tile late.  (An experiment, off by
-    // default: see launch_v6.)
-    int bid = blockIdx.x;
-    if (slot) {
-        const int xcd = blockIdx.x & 7;
-        volatile unsigned* box = (volatile unsigned*)smem;
-        if (tid == 0) box[0] = __hip_atomic_fetch_add(slot + xcd, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        bid = 8 * (int)__builtin_amdgcn_readfirstlane(box[0]) + xcd;
-        __syncthreads();                                   // everyone has read the ticket before the first LDS-DMA piece may land on it
-        if (bid >= map.tiles_m * tiles_n) {
-            if (tid == 0) {                                // the last workgroup to leave re-arms the ticket block (as in gemm_bf16_v7.hip)
-                const unsigned left = __hip_atomic_fetch_add(slot + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (left == gridDim.x - 1)
-                    for (int i = 0; i < 9; ++i) __hip_atomic_store(slot + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            MEDP_PROF_LEAVE(p.prof, p.prof_flags);
-            return;
-        }
-    }
+    const int bid = blockIdx.x;                 // workgroup b owns tile b
     int m0, n0;
     map.origin(bid, 8, 4, BM, m0, n0);          // bands of 8 row-tiles x super-columns of 4 column-tiles = one round of an XCD's 32 CUs
     const int nkt = (p.K + 63) >> 6;
@@ -196,14 +171,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
     };
     const bool has_res = p.residual != nullptr;
     if (has_res) load_res(0);
-    // LayerNorm fold (gemm_variants.h).  Consumer: the row's mean / rstd from the producer's per-tile partial sums, summed in tile order;
-    // C = rstd acc - rstd mean colsum + bias.  Producer: bf16 copy of the fp32 result + this tile's (sum, sum of squares) per row.
-    const MedpGemmFold& fo = p.fold;
-    const bool consumer = GR == 128 && fo.stats_in != nullptr, producer = GR == 128 && fo.c2 != nullptr;   // (launch_v6: no fold with GR 112)
-    f32x4 cs4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (consumer && n < p.N) cs4 = *(const f32x4*)(fo.colsum + n);
-    const float inv_dim = consumer ? 1.0f / (float)fo.ln_dim : 0.f;
-    float* sst = (float*)(smem + LDS_STATS);
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
 #pragma unroll
@@ -218,67 +185,14 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_v6_kernel(const MedpGemmA
             const int rr = it * 4 + er;
             const int m = m0 + wm * GR + half * 64 + rr;
             f32x4 v = *(const f32x4*)(wl + rr * 68 + ec);
-            float s1 = 0.f, s2 = 0.f;
             if (m < p.M && n < p.N) {
-                if (consumer) {
-                    float a1 = 0.f, a2 = 0.f;
-                    for (int t = 0; t < fo.stats_tiles; ++t) {
-                        const float2 st = *(const float2*)(fo.stats_in + ((size_t)m * fo.stats_tiles + t) * 2);
-                        a1 += st.x;
-                        a2 += st.y;
-                    }
-                    const float mean = a1 * inv_dim;
-                    const float rstd = rsqrtf(fmaxf(a2 * inv_dim - mean * mean, 0.f) + fo.ln_eps);
-                    v = v * rstd - (mean * rstd) * cs4 + bias4;
-                } else {
-                    v += bias4;
-                }
+                v += bias4;
                 v = gemm_act_scale<true>(v, scale4, p.act, p.out_bf16);
                 if (has_res) v += res[half][it];
                 gemm_store4<true>(p.C, p.ldc, p.out_bf16, m, n, v);      // non-temporal
-                if (producer) {
-                    uint2 o;
-                    o.x = pack_bf2(v[0], v[1]);
-                    o.y = pack_bf2(v[2], v[3]);
-                    *(uint2*)((bf16_t*)fo.c2 + (size_t)m * fo.ldc2 + n) = o;          // read next by the consumer GEMM: default cache policy
-                    s1 = (v[0] + v[1]) + (v[2] + v[3]);
-                    s2 = (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-                }
-            }
-            if (producer) {                         // the row's 64 columns of this wave: butterfly over the 16 lanes (one DPP row) that share it
-                // DPP operands (VALU rate), not __shfl_xor (ds_bpermute: an LDS round trip per step): quad xor 1, quad xor 2, then the two
-                // mirrors — after the quad steps all four lanes of a quad agree, so mirroring pairs quads / halves
-                auto row16_sum = [](float x) {
-                    x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, true));     // quad_perm [1,0,3,2]
-                    x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, true));     // quad_perm [2,3,0,1]
-                    x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x141, 0xF, 0xF, true));    // row_half_mirror
-                    x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x140, 0xF, 0xF, true));    // row_mirror
-                    return x;
-                };
-                s1 = row16_sum(s1);
-                s2 = row16_sum(s2);
-                if ((lane & 15) == 0) *(float2*)(sst + ((wm * 128 + half * 64 + rr) * 4 + wn) * 2) = make_float2(s1, s2);
             }
         }
         MEDP_WAVE_LDS_SYNC();
-    }
-    if (producer) {                                 // the four column waves' partials of a row, added in wave order: one (sum, sum sq) per row and tile
-        __syncthreads();
-        if (tid < 256 && m0 + tid < ((p.M + 255) & ~255)) {
-            float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float2 st = *(const float2*)(sst + (tid * 4 + q) * 2);
-                a1 += st.x;
-                a2 += st.y;
-            }
-            *(float2*)(fo.stats_out + ((size_t)(m0 + tid) * tiles_n + n0 / BN) * 2) = make_float2(a1, a2);
-        }
-    }
-    if (slot && tid == 0) {
-        const unsigned left = __hip_atomic_fetch_add(slot + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (left == gridDim.x - 1)
-            for (int i = 0; i < 9; ++i) __hip_atomic_store(slot + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     MEDP_PROF_LEAVE(p.prof, p.prof_flags);
 }
@@ -290,13 +204,7 @@ int launch_v6_buf(const MedpGemmArgs& a, hipStream_t stream) {
     MEDP_ONCE_PER_DEVICE({
         hipFuncSetAttribute((const void*)gemm_bf16_nt_v6_kernel<TAG, GR, BUF>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     });
-    // MEDP_V6_TICKETS=1: one-round grids launch 256 workgroups that queue for the tiles (see the kernel).  OFF by default: the
-    // hypothesis it tests — proj / fc2 run 30-40 % slower inside the step because workgroups start late on CUs still holding the
-    // other branch's short kernels — did not hold (in-box A/B: proj 41.9 us static, 44.2 us queued; step 5.03 vs 5.12 ms; alone the
-    // ticket costs 1.2 us): what the other branch takes from these GEMMs is cache and memory bandwidth, not CU slots.
-    static const int tickets_on = medp_env_int("MEDP_V6_TICKETS", 0);
-    unsigned* slot = (tickets_on && tiles >= 64 && tiles < 256) ? medp_gemm_ticket_block(stream) : nullptr;
-    gemm_bf16_nt_v6_kernel<TAG, GR, BUF><<<slot ? 256 : tiles, 512, LDS_BYTES, stream>>>(a, slot);
+    gemm_bf16_nt_v6_kernel<TAG, GR, BUF><<<tiles, 512, LDS_BYTES, stream>>>(a);
     MEDP_LAUNCH_CHECK("medp_gemm_bf16_nt(v6)");
     return 0;
 }
@@ -311,13 +219,12 @@ int launch_v6_gr(const MedpGemmArgs& a, hipStream_t stream) {
 
 // 224 x 256 tiles (GR = 112) for N = 768 where 256 x 256 tiles leave part of the chip idle: proj / fc2 at M = 64 x 257 are
 // 65 x 3 = 195 tiles of 256 rows on 256 CUs, 74 x 3 = 222 of 224 rows.  Taken for the launches with a residual (proj / fc2)
-// and no LayerNorm fold.  MEDP_V6_N768=0: always 256 x 256 (A/B runs); 2: also the N = 768 launches without a residual.
+// only.  MEDP_V6_N768=0: always 256 x 256 (A/B runs); 2: also the N = 768 launches without a residual.
 bool v6_use_224(const MedpGemmArgs& a) {
     static const int mode = medp_env_int("MEDP_V6_N768", 1);
     const int tiles256 = ((a.M + 255) / 256) * ((a.N + 255) / 256);
     const int tiles224 = ((a.M + 223) / 224) * ((a.N + 255) / 256);
-    return mode != 0 && a.N == 768 && (a.residual != nullptr || mode == 2) && a.fold.c2 == nullptr && a.fold.stats_in == nullptr &&
-           tiles256 < 256 && tiles224 <= 256;
+    return mode != 0 && a.N == 768 && (a.residual != nullptr || mode == 2) && tiles256 < 256 && tiles224 <= 256;
 }
 
 }  // namespace

@@ -56,13 +56,11 @@
 //     would be READ (up to 255 rows past the operand's end) — the results would still be right, by the next point, the reads not;
 //   * a lane past num_records reads nothing and writes ZEROS to LDS, as the zero chunk did — but nothing depends on it: a row of
 //     A at or past M only ever feeds output rows >= M, a row of W at or past N only output columns >= N, and neither is stored
-//     (every epilogue tests m < M and n < N per element, or runs on a tile that lies wholly below M and N; the LayerNorm-fold producer
-//     adds only stored elements into its row sums and writes zeros for the rows between M and the next multiple of 256; the consumer
-//     reads row statistics, not LDS rows).  Rows 112-127 of a group's A half under 224-row tiles lie past their descriptor (48 rows)
-//     and are skipped at compile time by read_a / mma.  Whatever such LDS rows hold — zeros or a previous K-tile — cannot reach a
-//     stored element.
-// The one-tile kernel keeps the per-lane form for K % 64 != 0 (chunks past K INSIDE a K-tile need a select per lane); the bias,
-// column-sum and row-statistics side streams stay on glds16.
+//     (every epilogue tests m < M and n < N per element, or runs on a tile that lies wholly below M and N).  Rows 112-127 of a
+//     group's A half under 224-row tiles lie past their descriptor (48 rows) and are skipped at compile time by read_a / mma.
+//     Whatever such LDS rows hold — zeros or a previous K-tile — cannot reach a stored element.
+// The one-tile kernel keeps the per-lane form for K % 64 != 0 (chunks past K INSIDE a K-tile need a select per lane); the bias
+// side stream stays on glds16.
 #pragma once
 #include "common.h"
 

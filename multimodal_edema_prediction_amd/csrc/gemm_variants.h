@@ -2,21 +2,6 @@
 // gemm_bf16_v6.hip, gemm_bf16_v7.hip, gemm_ragged_rows.hip) and the internal callers (vit.hip); not part of the C ABI.
 #pragma once
 #include "gemm_profile.h"
-// LayerNorm folded into the block GEMMs of the CXR encoder (vit.hip): LN(x) W^T + b = rstd (x (W g)^T) - rstd mean colsum(W g) + (b + W beta).
-//   PRODUCER (proj / fc2: fp32 residual output x): also writes c2 = bf16(x) and, per row and 256-column tile, the (sum, sum of squares)
-//     of the fp32 values into stats_out [rows padded to 256][tiles_n][2].
-//   CONSUMER (qkv / fc1: A = bf16(x), W = bf16(W g)): C = rstd[m] acc - rstd[m] mean[m] colsum[n] + bias[n] (then GELU), mean / rstd from
-//     stats_in [rows padded to 256][stats_tiles][2] over ln_dim columns.
-struct MedpGemmFold {
-    void* c2 = nullptr;                 // producer: bf16 copy of C
-    int ldc2 = 0;
-    float* stats_out = nullptr;
-    const float* stats_in = nullptr;    // consumer
-    int stats_tiles = 0;
-    const float* colsum = nullptr;
-    float ln_eps = 0.f;
-    int ln_dim = 0;
-};
 // The operands of one GEMM, from the C entry points to the launchers.  The 256-tile kernels take the struct by value as their first
 // kernel argument: a new field moves the offsets of the arguments behind it.
 struct MedpGemmArgs {
@@ -30,13 +15,10 @@ struct MedpGemmArgs {
     int ldr, act, out_bf16;
     unsigned long long* prof;   // optional in-kernel launch clock (gemm_profile.h)
     int prof_flags;      // 1: do not stamp the arrival, 2: do not stamp the departure (a GEMM issued as two launches shares one clock)
-    MedpGemmFold fold;   // all null: a plain GEMM
 };
 // The front end (gemm_bf16.hip): argument checks, gemm_plan, launch.  tag 1 = the CXR-encoder block GEMMs: their own kernel symbols
-// and the launch clock.  `workspace` (may be null) allows split-K (medp_gemm_nt_workspace_bytes).  A LayerNorm fold (a.fold) is an
-// argument error on a shape that does not take the 256-tile kernels: ask medp_gemm_fold_eligible first.
+// and the launch clock.  `workspace` (may be null) allows split-K (medp_gemm_nt_workspace_bytes).
 int medp_gemm_run(const MedpGemmArgs& a, int tag, float* workspace, size_t workspace_bytes, void* stream);
-bool medp_gemm_fold_eligible(int M, int N, int K);
 
 // ---- launchers, one per kernel family (which shape takes which: gemm_plan) ----
 // gemm_bf16_tiles.hip: 128 x bn tiles (bn 64 or 128; partial / nsplit > 1: split-K with its finish pass) and v3 (256 x 128 tiles)
@@ -50,6 +32,4 @@ int medp_gemm_ragged_rows_launch(const MedpGemmArgs& a, int m_begin, void* strea
 bool medp_gemm_v7_eligible(const MedpGemmArgs& a);
 // what the kernel itself asks of a launch (medp_gemm_v7_eligible: this and a grid of more than one round of 256 workgroups)
 bool medp_gemm_v7_supports(const MedpGemmArgs& a);
-// a private block of per-XCD ticket counters for ONE launch on `stream` (gemm_bf16_v7.hip; nullptr: none left)
-unsigned* medp_gemm_ticket_block(void* stream);
 int medp_gemm_v7_launch(const MedpGemmArgs& a, int tag, void* stream);

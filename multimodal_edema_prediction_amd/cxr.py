@@ -152,13 +152,6 @@ class Dinov2Backbone(nn.Module):
             L.fc1_w, L.fc1_b = ptr(bf(blk.w1)), ptr(f32(blk.b1))
             L.fc2_w, L.fc2_b = ptr(bf(blk.w2)), ptr(f32(blk.b2))
             L.ls2 = ptr(f32(blk.ls2))
-            # LayerNorm fold operands (include/medp_hip.h): W g in bf16, the row sums of THAT rounded matrix, b + W beta
-            for name, W, b, g, beta in (("qkv", qkv_w, qkv_b, blk.ln1_w, blk.ln1_b), ("fc1", blk.w1, blk.b1, blk.ln2_w, blk.ln2_b)):
-                W32 = W.detach().to(torch.float32)
-                wg = bf(W32 * g.detach().to(torch.float32)[None, :])
-                setattr(L, name + "_wg", ptr(wg))
-                setattr(L, name + "_cs", ptr(f32(wg.to(torch.float32).sum(dim=1))))
-                setattr(L, name + "_b2", ptr(f32(b.detach().to(torch.float32) + W32 @ beta.detach().to(torch.float32))))
         w = MedpVitWeights()
         w.hidden, w.n_layers, w.n_heads, w.mlp_hidden = D, c.num_hidden_layers, c.num_attention_heads, D * c.mlp_ratio
         w.patch, w.pos_side, w.patch_kpad, w.ln_eps = c.patch_size, c.image_size // c.patch_size, pw.shape[1], c.layer_norm_eps

@@ -31,8 +31,21 @@ def test_library_builds_and_exports_every_declared_symbol():
 
 def test_version_and_arch():
     L = abi.lib()
-    assert L.medp_version() >= 1
+    assert L.medp_version() == abi.ABI_VERSION
     assert L.medp_arch() == b"gfx950"
+
+
+def test_library_of_another_abi_version_is_refused(monkeypatch):
+    """A library whose medp_version() differs from abi.ABI_VERSION lays the weight structs out differently: lib() must not hand it out."""
+    built = abi.lib().medp_version()
+    monkeypatch.setattr(abi, "_lib", None)
+    monkeypatch.setattr(abi, "ABI_VERSION", built + 1)
+    with pytest.raises(RuntimeError) as e:
+        abi.lib()
+    msg = str(e.value)
+    assert f"ABI version {built}" in msg and f"expects {built + 1}" in msg
+    assert "multimodal_edema_prediction_amd.build --force" in msg and "--trace" in msg and "--ablate" in msg
+    assert abi._lib is None                             # nothing was cached for the next caller
 
 
 def test_invalid_arguments_are_reported_without_a_gpu():

@@ -1,5 +1,5 @@
 """Register resources of the persistent block GEMM (csrc/gemm_bf16_v7.hip), read from the kernel metadata of its gfx950 code object
-(the amdhsa.kernels note: counts only, no instruction text).  The plain kernel <TAG, false> keeps every value in registers — its
+(the amdhsa.kernels note: counts only, no instruction text).  The kernel <TAG> keeps every value in registers — its
 `s_waitcnt vmcnt(N)` waits are counted by hand, a scratch access would shift them — and, with one buffer descriptor per operand
 instead of four, spills 35 SGPRs to VGPR lanes where it spilled 57 with eight descriptors held across the K-loop (none of the 35 inside
 the K-loop: tools/count_epilogue_insts.py lists the v_readlane / v_writelane of the K-loop and of the epilogue)."""
@@ -40,8 +40,8 @@ def _kernel_metadata(src: str, tmp: str) -> dict:
 def test_plain_persistent_kernel_resources():
     with tempfile.TemporaryDirectory() as tmp:
         kernels = _kernel_metadata("gemm_bf16_v7.hip", tmp)
-    plain = {k: v for k, v in kernels.items() if re.search(r"gemm_bf16_nt_v7_kernelILi\d+ELb0E", k)}
-    assert len(plain) == 2, f"expected the two plain instantiations, found {sorted(kernels)} (metadata format changed?)"
+    plain = {k: v for k, v in kernels.items() if re.search(r"gemm_bf16_nt_v7_kernelILi\d+EE", k)}
+    assert len(plain) == 2, f"expected the two instantiations, found {sorted(kernels)} (metadata format changed?)"
     for k, v in plain.items():
         assert set(v) == {"vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size"}, (k, v)
         assert v["private_segment_fixed_size"] == 0, f"{k} uses scratch: {v}"

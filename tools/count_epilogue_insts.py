@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What the persistent block GEMM (csrc/gemm_bf16_v7.hip) executes per tile outside its K-loop, counted in the gfx950 assembly of the
-plain kernel <1, false>.  Needs hipcc, no GPU.
+tagged kernel <1>.  Needs hipcc, no GPU.
 
     python tools/count_epilogue_insts.py [BASE]
 
@@ -21,7 +21,7 @@ import tempfile
 
 from diff_kernel_isa import ROOT, assembly, extract
 
-KERNEL = re.compile(r"^(_Z\S*gemm_bf16_nt_v7_kernelILi1ELb0E\S*):")
+KERNEL = re.compile(r"^(_Z\S*gemm_bf16_nt_v7_kernelILi1E(?:Lb0E)?E\S*):")      # (Lb0E: the <1, false> of a BASE from before the FOLD parameter left)
 LANE = ("v_readlane", "v_writelane")
 PLAN = ("v_mfma", "ds_read", "buffer_load", "global_load", "s_barrier", "s_waitcnt", "s_setprio")      # what the phase plan of gemm_tile256.h orders
 
@@ -94,7 +94,7 @@ def main():
         for label, tree in trees:
             body = kernel_body(assembly(tree, "gemm_bf16_v7.hip", ""))
             region, full = epilogue(body)
-            print(f"{label}: gemm_bf16_nt_v7_kernel<1, false>")
+            print(f"{label}: gemm_bf16_nt_v7_kernel<1>")
             print(f"  epilogue, all paths     {fmt(counts(region))}")
             for r in full:
                 gelu = sum(x.startswith("v_pk_fma_f32") for x in r) > 64

@@ -10,7 +10,7 @@
       /opt/skills/guides/MI355X_MICROARCH.md), WRITE_SIZE as is, KiB -> bytes; per kernel and launch-weighted mean."""
 import collections, csv, datetime, glob, json, os, subprocess, sys
 
-GEMMS = ("gemm_bf16_nt_v6_kernel<1,", "gemm_bf16_nt_v7_kernel<1,")    # (both carry a second template argument: v6 <1, 128> / <1, 112>, v7 <1, false> / <1, true>)
+GEMMS = ("gemm_bf16_nt_v6_kernel<1,", "gemm_bf16_nt_v7_kernel<1>")    # (v6 carries further template arguments: <1, 128, ...> / <1, 112, ...>; v7 is <TAG> alone)
 
 
 def commit():
