@@ -794,6 +794,67 @@ int medp_mlp_head_train_epoch(const MedpMlpHeadProblem* table_host, const MedpMl
 int medp_mlp_head_scores(const float* X, long long ldx, int N, int col0, int K, int H, int L, const float* W1, const float* b1,
                          const float* W2, const float* b2, const int* rows, int n, float* logits, double* probs, void* stream);
 
+/* ---- Gradient-flow diagnostics of the dual teacher (csrc/grad_flow.hip) --------------------------------------------------------
+ * The reductions around ONE backward pass over a replicated query bank (grad_flow_diagnostics.py): replica g = (branch, label) of
+ * the K pathology queries is seeded with that label's loss cotangent only, so its slice of the replicated leaf's gradient is
+ * d(lw_k per_k^branch) / d queries.  fp32 inputs read in place, fp64 accumulators, no floating-point atomics, every accumulator
+ * element has one owner, sums over samples go through per-sample partials and a fixed-order workgroup sum: two runs from the same
+ * state are bit-identical.  Branch order everywhere: img, ts, fus.  K <= MEDP_GRAD_FLOW_MAX_K, D <= MEDP_GRAD_FLOW_MAX_D,
+ * B <= MEDP_GRAD_FLOW_MAX_B; a null pointer (other than the nullable ones named below) or a size outside its range: rc < 0,
+ * nothing launched.
+ *
+ * medp_grad_flow_seeds: logits img / ts / fus [B, K], y, mask [B, K], label_weights [K], pos_weight [K] or null, eps ->
+ *     losses  [3, K] fp32      lw_k per_k^branch (per = the masked BCE mean of medp_dual_pathology_loss, whose kernel computes it:
+ *                              this call launches it with unit alphas into `ws` and scatters its gradients)
+ *     cot_img [B, K, K]        replica g of the image pass: column g = lw_g d per_g^img / d logit[b, g], zero elsewhere
+ *     cot_ts  [B, 2K, K]       replica g < K of the time-series pass: column g likewise for the ts branch; replicas g >= K zero
+ *     cot_fus [B, 2K, K]       replica K + g: column g for the fusion branch; replicas g < K zero
+ *   ws: 4 + 3K + 3BK floats, contents undefined afterwards.
+ *
+ * medp_grad_flow_accumulate: one call per batch adds to `state` (medp_grad_flow_state_doubles(K, D) doubles, zeroed by the caller):
+ *     [0, 3 K K D)             per_label_grad_sums [3, K_label, K, D] += dq
+ *     + 3                      loss_sums [3]                          += sum_k losses[r, k]
+ *     + 4                      batch_cos_sum += c, negative_count += (c < 0), batch_count += 1, sample_count += B, where
+ *                              c = cos(sum_k dq[img, k], sum_k dq[ts, k])  (the branch gradients, by linearity)
+ *     + K                      valid_label_count [K]                  += sum_b mask[b, k]
+ *     + 4                      fusion sensitivity img_raw, ts_raw, img_scaled, ts_scaled: raw = sum_b ||g_b||, scaled =
+ *                              sum_b ||g_b|| ||token_b||, norms over the sample's flattened [K, D], g_b = sum_k dX[b, k]
+ *     + 4 K                    the same four per label, [4, K], g_b = dX[b, k]
+ *   dq [3, K_label, K, D]; dT [B, K_label, K, D] the fusion replicas' gradients w.r.t. the ts tokens; dI likewise for the image
+ *   tokens or null (= zeros: fusion_logits does not depend on them); I, T [B, K, D] the tokens; mask [B, K]; losses [3, K].
+ *   ws: medp_grad_flow_ws_doubles(B, K) doubles.  Cosines follow the reference's rule: a denominator <= 1e-12 gives 0.  Two launches.
+ *
+ * medp_grad_flow_report: state, the three alphas -> out [MEDP_GRAD_FLOW_REPORT_HEAD + MEDP_GRAD_FLOW_REPORT_PER_LABEL K] fp64:
+ *     4 r + (0 .. 3)           branch r: loss, ||g||, ||alpha g||, cos(alpha g, sum_r alpha_r g_r)
+ *     12 .. 16                 cos img-ts, img-fus, ts-fus of the mean gradients, batch cosine mean, negative batch fraction
+ *     17                       ||alpha_img g_img|| / max(||alpha_ts g_ts||, 1e-12)
+ *     18 .. 23                 sensitivities / max(samples, 1) in the state's order, raw img / ts, scaled img / ts (max(., 1e-12))
+ *     24, 25                   batches, samples
+ *     HEAD + 16 k + (0 .. 15)  label k: valid samples; ||g|| per branch; cos img-ts, img-fus, ts-fus; ||sum_r alpha_r g_r||; the
+ *                              own-row fractions ||g_r[k, k, :]|| / max(||g_r[k]||, 1e-12) per branch; the four sensitivities
+ *                              / max(valid, 1); scaled img / ts
+ *   Gradients are means over batches (/ max(batch_count, 1)).  The mean BRANCH gradients are the label sums of the per-label means;
+ *   the reference accumulates separately computed branch totals, equal up to rounding.
+ *
+ * medp_query_geometry: rows [3, K, D] fp32 (the raw prototypes, the image-effective and the ts-effective queries) -> out fp64
+ *   [3 K K + K + 1]: the three Gram matrices of the rows divided by max(||row||, 1e-12), the K prototype norms (rows[0]) and
+ *   ||G_img - G_ts||_F / K. */
+#define MEDP_GRAD_FLOW_MAX_K 16
+#define MEDP_GRAD_FLOW_MAX_D 4096
+#define MEDP_GRAD_FLOW_MAX_B 4096
+#define MEDP_GRAD_FLOW_REPORT_HEAD 26
+#define MEDP_GRAD_FLOW_REPORT_PER_LABEL 16
+size_t medp_grad_flow_state_doubles(int K, int D);
+size_t medp_grad_flow_ws_doubles(int B, int K);
+int medp_grad_flow_seeds(const float* img, const float* ts, const float* fus, const float* y, const float* mask,
+                         const float* label_weights, const float* pos_weight, float eps, float* ws, float* losses, float* cot_img,
+                         float* cot_ts, float* cot_fus, int B, int K, void* stream);
+int medp_grad_flow_accumulate(const float* dq, const float* dI, const float* dT, const float* I, const float* T, const float* mask,
+                              const float* losses, double* state, double* ws, int B, int K, int D, void* stream);
+int medp_grad_flow_report(const double* state, double alpha_img, double alpha_ts, double alpha_fus, double* out, int K, int D,
+                          void* stream);
+int medp_query_geometry(const float* rows, double* out, int K, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -215,6 +215,12 @@ SIGNATURES = {
     "medp_mlp_head_supported": (I, [I, I, I, I]),
     "medp_mlp_head_train_epoch": (I, [P, P, I, P]),
     "medp_mlp_head_scores": (I, [P, LL, I, I, I, I, I, P, P, P, P, P, I, P, P, P]),
+    "medp_grad_flow_state_doubles": (SZ, [I, I]),
+    "medp_grad_flow_ws_doubles": (SZ, [I, I]),
+    "medp_grad_flow_seeds": (I, [P, P, P, P, P, P, P, F, P, P, P, P, P, I, I, P]),
+    "medp_grad_flow_accumulate": (I, [P, P, P, P, P, P, P, P, P, I, I, I, P]),
+    "medp_grad_flow_report": (I, [P, c_double, c_double, c_double, P, I, I, P]),
+    "medp_query_geometry": (I, [P, P, I, I, P]),
     "medp_rng_set_epoch_ptr": (I, [P]),
     "medp_counter_advance": (I, [P, P]),
 }
